@@ -157,7 +157,7 @@ FORCE_EXCHANGE = os.environ.get("LIST_BENCH_FORCE_EXCHANGE", "0") == "1"
 
 
 def run_config(args, precision, steps, warmup, inp, hip, ev, world, device, gather_fn, sustained_steps=0, fused_fc0=True,
-               img_proj=None):
+               img_proj=None, keep_last=False):
     import torch
     import torch.distributed as dist
     multi = world > 1 or FORCE_EXCHANGE
@@ -271,6 +271,13 @@ def run_config(args, precision, steps, warmup, inp, hip, ev, world, device, gath
         elapsed_local, elapsed = elapsed, float(t.item())
     else:
         elapsed_local = elapsed
+    extra = {"elapsed_local_s": elapsed_local}
+    if keep_last:
+        # what the LAST timed step handed its caller, copied before the untimed steps below reuse the buffers
+        k = (n_calls[0] - 1) % len(sdfs)
+        extra["last_outputs"] = {"sdf": sdfs[k].clone()}
+        if multi:
+            extra["last_outputs"]["sdf_gathered"] = gathered[k].clone()
     for ev_set in detail_events:              # untimed: per-gather durations, the gathers one after the other
         step(ev_set)
     drain()
@@ -318,7 +325,6 @@ def run_config(args, precision, steps, warmup, inp, hip, ev, world, device, gath
     # HIP-event time of every timed step (first launch .. behind the last one, on the stream they run on)
     step_ms = sorted(ev.elapsed_ms(pre[0], pre[4]) for pre, _ in step_events)
     q = lambda f: step_ms[min(len(step_ms) - 1, int(f * len(step_ms)))]
-    extra = {"elapsed_local_s": elapsed_local}
     if multi:
         # once, outside the timed region: what the exchange delivered holds this rank's shard at this rank's offset, and
         # every other rank's rows are finite numbers (not the zeros the buffer was born with)
@@ -627,6 +633,33 @@ def path_roofs(value, precision, grid=False):
     return r
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32 (float64 kept as it is).  When they would exceed
+    DUMP_BUDGET_BYTES together, each is replaced by the same fixed sample of its flattened elements (seed 0, sorted
+    indices, the same share of every array), so two runs with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    room = DUMP_BUDGET_BYTES - 4096 * len(host)
+    written = {}
+    for name, a in host.items():
+        shape = list(a.shape)
+        if total > room:
+            k = int(a.size * (room / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": shape, "dtype": str(a.dtype), "elements_written": int(a.size),
+                         "sample": "seeded (0) sorted sample of the flattened array" if a.size < np.prod(shape) else None}
+    return written
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: start N ranks with torch.distributed.run as a child process (the
     driver's own N > 1 command line), pass its output through and return its exit code."""
@@ -668,7 +701,14 @@ def main():
     ap.add_argument("--plumbing-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-sample-points", type=int, default=50000,
                     help="points per image of the CPU baseline sample (bounds the 256^3 grid workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned (sdf; with N > 1 ranks also the all-gathered "
+                         "sdf) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started the way the driver starts the N = 1 case (`python bench.py --gpus N`, no launcher): this process
@@ -748,7 +788,11 @@ def main():
     headline = args.precision or ("bf16x3" if grid else "fp16")
     alt_prec = "fp16" if headline == "bf16x3" else "bf16x3"
     elapsed, kernel_ms, sdf, extra = run_config(args, headline, args.steps, args.warmup, inp, hip, ev, world,
-                                                device, gather_fn, sustained_steps=args.sustained_steps)
+                                                device, gather_fn, sustained_steps=args.sustained_steps,
+                                                keep_last=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(args.dump_outputs, extra.pop("last_outputs"))
+        print(f"bench: last timed step's outputs written to {args.dump_outputs}: {json.dumps(written)}", file=sys.stderr)
     alt_cl = None
     if args.precision is None and not args.no_channels_last_alt:
         # same workload with the maps already in the layout MI355X-first producers emit (SURVEY 8 f2:

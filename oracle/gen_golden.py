@@ -347,6 +347,19 @@ def dataset_goldens(torch):
     with open(os.path.join(OUT, "dataset_lists.json"), "w") as f:
         json.dump(lists, f, indent=0, sort_keys=True)
     np.savez_compressed(os.path.join(OUT, "dataset_items.npz"), **out)
+    # the split lists themselves, byte for byte, for tests/test_dataset_golden.py (reproducible archive: fixed order,
+    # owner and times)
+    import tarfile
+
+    def _plain(ti):
+        ti.uid = ti.gid = 0
+        ti.uname = ti.gname = ""
+        ti.mtime = 0
+        return ti
+    with tarfile.open(os.path.join(OUT, "disn_split.tar.xz"), "w:xz", preset=9) as t:
+        t.add(split, arcname="DISN_split", recursive=False, filter=_plain)
+        for fn in sorted(os.listdir(split)):
+            t.add(os.path.join(split, fn), arcname="DISN_split/" + fn, filter=_plain)
     print("datasets:", len(lists) - 1, "lists;", int(out["n_items"]), "IM2SDF items,", int(out["n_items_pf"]), "point items")
 
 

@@ -76,3 +76,25 @@ def test_profile_summaries_name_kernels_that_rocprof_left_mangled():
     assert pmc_traffic.kernel_key("_ZN4list14k_mlp_tail_f16ENS_10TailParamsE", 320000, 0) == "fc_2_out"
     assert pmc_traffic.kernel_key("void list::k_gemm_nt_pp<0, 1, true, 0>(list::GemmParams)", 640000, 0) == "fc_0"
 
+
+
+def test_dumped_outputs_stay_within_budget_and_sample_the_same_points(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files, whole arrays while they fit, beyond the budget the same seeded sample every run."""
+    import numpy as np
+    import torch
+    small = torch.arange(12, dtype=torch.float16).reshape(3, 4)
+    w = bench.dump_outputs(str(tmp_path / "a"), {"sdf": small})
+    got = np.load(tmp_path / "a" / "sdf.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4) and np.array_equal(got, small.float().numpy())
+    assert w["sdf"]["sample"] is None
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4096 + 4000)       # room for 1000 float32 of 2 x 1000
+    big = {"sdf": torch.randn(10, 100), "sdf_gathered": torch.randn(20, 50, dtype=torch.float64)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    sizes = 0
+    for name in big:
+        b, c = np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy")
+        assert np.array_equal(b, c) and b.dtype == (np.float64 if name == "sdf_gathered" else np.float32)
+        assert np.isin(b, big[name].numpy().ravel()).all()                # values of the array, not something else
+        sizes += os.path.getsize(tmp_path / "b" / f"{name}.npy")
+    assert sizes <= bench.DUMP_BUDGET_BYTES

@@ -3,7 +3,7 @@
 tests/golden/dataset_lists.json and dataset_items.npz come from oracle/gen_golden.py --datasets-only, which parsed
 the reference's own split lists (data/DISN_split/*.lst) with the reference's reader and ran the reference's
 datasets.Datasets.IM2SDF / IM2PointFarthest over the synthetic tree of oracle/dataset_fixture.py.  Here this
-package's readers see the same lists and an identical tree."""
+package's readers see the same lists (stored in tests/golden/disn_split.tar.xz) and an identical tree."""
 import hashlib
 import json
 import os
@@ -16,7 +16,17 @@ from list_amd import arguments, utils
 from list_amd.datasets import Datasets as D
 from oracle import dataset_fixture as DF
 
-SPLIT = "/root/reference/data/DISN_split"
+
+@pytest.fixture(scope="module")
+def split_dir(golden_dir, tmp_path_factory):
+    """The reference's own split lists, stored byte for byte in tests/golden/disn_split.tar.xz (DISN_split/*.lst)."""
+    import tarfile
+    root = tmp_path_factory.mktemp("split")
+    with tarfile.open(os.path.join(golden_dir, "disn_split.tar.xz")) as t:
+        for m in t.getmembers():
+            assert m.isdir() or (m.isfile() and m.name.startswith("DISN_split/") and ".." not in m.name), m.name
+        t.extractall(root)
+    return os.path.join(str(root), "DISN_split")
 
 
 @pytest.fixture(scope="module")
@@ -24,20 +34,19 @@ def lists(golden_dir):
     return json.load(open(os.path.join(golden_dir, "dataset_lists.json")))
 
 
-@pytest.mark.skipif(not os.path.isdir(SPLIT), reason="the reference's split lists live in the authoring container only")
-def test_split_lists_parse_like_the_reference_reader(lists):
+def test_split_lists_parse_like_the_reference_reader(lists, split_dir):
     """Datasets.py:293-298 over every list the reference ships: same ids, same order."""
     n = 0
     for fn, want in lists.items():
         if fn.startswith("_"):
             continue
-        ids = D._read_shape_ids(os.path.join(SPLIT, fn))
+        ids = D._read_shape_ids(os.path.join(split_dir, fn))
         assert len(ids) == want["count"] and ids[0] == want["first"] and ids[-1] == want["last"], fn
         assert hashlib.sha256("\n".join(ids).encode()).hexdigest() == want["sha256"], fn
         n += 1
     assert n == 27
     # arguments.py:112-125: the first 30 lines of testlist_all.lst, category-filtered
-    cfg = arguments.default_config(testlist_file=os.path.join(SPLIT, "testlist_all.lst"))
+    cfg = arguments.default_config(testlist_file=os.path.join(split_dir, "testlist_all.lst"))
     got = [[t["cat_id"], t["shape_id"], t["cam_id"]] for t in cfg.testlist]
     want = [t for t in lists["testlist_all.lst"]["first30"] if t[0] in cfg.catlist]
     assert got == want and len(got) > 0
