@@ -23,6 +23,8 @@ def build_parser():
     p.add_argument("--mcube_znum", type=int, default=128,
                    help="resolution of the inference query grid (decoupled from --vox_res)")
     p.add_argument("--test_pointnum", type=int, default=65536)
+    p.add_argument("--save_volume", action="store_true",
+                   help="test.py: also write each item's raw SDF volume (<stem>_sdf.npy) next to its mesh")
     p.add_argument("--chunk_s", type=int, default=0)
     p.add_argument("--chunk_l", type=int, default=217)
     p.add_argument("--chunk_id", type=int, default=0)

@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import parallel, utils
+from .. import mesh, parallel, utils
 from . import losses as L
 
 
@@ -142,7 +142,8 @@ class LIST:
         img = batch["rgb_image"].to(self._device())
         transmat = batch["transmat"].to(self._device()) if "transmat" in batch else None
         volume, occ, vox_feat = self.predict_grid(img, transmat)
-        pred_mesh = utils.generate_mesh(volume.cpu().numpy(), -0.5, 0.5, as_trimesh_obj=True)
+        # marching cubes on the device, where the volume lies (mesh.marching_cubes: mcubes' surface of -volume at 0)
+        pred_mesh = mesh.Mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5))
         score = self.eval(pred_mesh, batch.get("gt_mesh")) if eval_pred else {}
         return [pred_mesh, occ, vox_feat[0].squeeze(1)], score
 

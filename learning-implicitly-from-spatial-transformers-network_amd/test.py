@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Inference entry point (test.py of the reference): for every test item, evaluate the SDF on the
-query grid with the HIP path and extract the iso-surface.
+query grid with the HIP path and extract the iso-surface on the GPU (mesh.marching_cubes), written as
+<results_dir>test_objs/<cat>/<shape>_<cam>_pred.obj.
 
     python test.py --model network.models.LIST --dataset datasets.Datasets.SyntheticIM2SDF -e run1 \
         --mcube_znum 256
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py ...    # query axis sharded over GPUs
 
-`--save_volume` writes the raw [res,res,res] SDF volume (npy) so that meshing can happen offline
-when PyMCubes/trimesh are not installed."""
+`--save_volume` also writes the raw [res,res,res] SDF volume (<stem>_sdf.npy)."""
 import os
 import sys
 import time
@@ -15,7 +15,7 @@ import time
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(_HERE))
 import list_amd                                          # noqa: E402
-from list_amd import arguments, utils                   # noqa: E402
+from list_amd import arguments, mesh, utils             # noqa: E402
 from list_amd.train import wrap_model                   # noqa: E402
 
 import numpy as np                                       # noqa: E402
@@ -23,7 +23,8 @@ import torch                                             # noqa: E402
 import torch.distributed as dist                         # noqa: E402
 
 
-def test_all(config, save_volume=True):
+def test_all(config, save_volume=None):
+    save_volume = getattr(config, "save_volume", False) if save_volume is None else save_volume
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -56,10 +57,11 @@ def test_all(config, save_volume=True):
             stem = utils.ensure_dir(out_dir + it["cat_id"] + "/") + f"{it['shape_id']}_{it['cam_id']}"
             if save_volume:
                 np.save(stem + "_sdf.npy", volume.cpu().numpy())
-            try:
-                utils.generate_mesh(volume.cpu().numpy(), -0.5, 0.5, as_trimesh_obj=True).export(stem + "_pred.obj")
-            except RuntimeError as e:
-                print("mesh extraction skipped:", e)
+            t0 = time.time()
+            m = mesh.Mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5))
+            dt = time.time() - t0
+            m.export(stem + "_pred.obj")
+            print(f"  mesh: {len(m.vertices)} vertices, {len(m.faces)} faces in {dt * 1e3:.1f} ms -> {stem}_pred.obj")
     if dist.is_initialized():
         dist.destroy_process_group()
 

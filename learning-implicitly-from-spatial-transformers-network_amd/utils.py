@@ -90,11 +90,23 @@ def get_kdtree(bb_min, bb_max, res):
 
 
 def generate_mesh(pred_values, bb_min, bb_max, as_trimesh_obj=False):
-    """Marching cubes of the NEGATED field at level 0 (reference utils.py:172-182)."""
+    """Marching cubes of the NEGATED field at level 0 (reference utils.py:172-182).  Without PyMCubes, the same surface
+    comes from mesh.marching_cubes_cpu (numpy); as_trimesh_obj then gives a trimesh.Trimesh if trimesh imports, else a
+    mesh.Mesh (it has export() too)."""
     try:
         import mcubes
-    except ImportError as e:
-        raise RuntimeError("PyMCubes is required for mesh extraction (not needed for SDF queries)") from e
+    except ImportError:
+        mcubes = None
+    if mcubes is None:
+        from . import mesh
+        verts, tris = mesh.marching_cubes_cpu(pred_values, 0.0, bb_min, bb_max)
+        if as_trimesh_obj:
+            m = mesh.Mesh(verts, tris)
+            try:
+                return m.to_trimesh()
+            except ImportError:
+                return m
+        return verts, tris
     verts, tris = mcubes.marching_cubes(-pred_values, 0)
     res = pred_values.shape[0]
     verts = verts * ((bb_max - bb_min) / (res - 1)) + bb_min
