@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import mesh, parallel, utils
+from .. import evaluate, mesh, parallel, utils
 from . import losses as L
 
 
@@ -148,8 +148,11 @@ class LIST:
         return [pred_mesh, occ, vox_feat[0].squeeze(1)], score
 
     def eval(self, pred, gt):
-        raise RuntimeError("mesh evaluation (evaluation/eval_util.py of the reference) is outside the "
-                           "scope of the query path; export the mesh and evaluate offline")
+        """eval_util.py:eval_mesh of the predicted mesh against the ground truth (a Mesh or a path to one), on the
+        executor's device -> the reference's dict of floats ({} for a prediction of fewer than 10 vertices)."""
+        if gt is None:
+            raise ValueError("LIST.eval: no ground-truth mesh (the batch carries no 'gt_mesh')")
+        return evaluate.eval_mesh(pred, gt, self.bb_min, self.bb_max, device=self._device())
 
     def save(self, batch, pred, fname):
         pred[0].export(fname + "_pred.obj")

@@ -7,7 +7,11 @@ query grid with the HIP path and extract the iso-surface on the GPU (mesh.marchi
         --mcube_znum 256
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py ...    # query axis sharded over GPUs
 
-`--save_volume` also writes the raw [res,res,res] SDF volume (<stem>_sdf.npy)."""
+`--save_volume` also writes the raw [res,res,res] SDF volume (<stem>_sdf.npy).  `--eval_pred` scores every item whose
+dataset gives a ground-truth mesh (evaluate.eval_mesh on the device: Chamfer-L2, precision / recall / F-score, IoU) and
+writes <results_dir>test_objs/<cat>.csv, one row per item and a final `Mean` row, as the reference does; items without
+one (the synthetic datasets) are reported as skipped."""
+import csv
 import os
 import sys
 import time
@@ -15,7 +19,7 @@ import time
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(_HERE))
 import list_amd                                          # noqa: E402
-from list_amd import arguments, mesh, utils             # noqa: E402
+from list_amd import arguments, evaluate, mesh, utils   # noqa: E402
 from list_amd.train import wrap_model                   # noqa: E402
 
 import numpy as np                                       # noqa: E402
@@ -23,8 +27,27 @@ import torch                                             # noqa: E402
 import torch.distributed as dist                         # noqa: E402
 
 
-def test_all(config, save_volume=None):
+def write_scores(path, rows):
+    """rows: [(ID, {metric: value})] -> the reference's CSV (pandas' to_csv of its DataFrame: an index column, `ID`,
+    the metrics, then a `Mean` row over the items), values rounded to 5 digits."""
+    keys = []
+    for _, score in rows:
+        keys += [k for k in score if k not in keys]
+    mean = {}
+    for k in keys:
+        vals = [score[k] for _, score in rows if k in score and not np.isnan(score[k])]
+        mean[k] = float(np.mean(vals)) if vals else float("nan")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["", "ID"] + keys)
+        for i, (ident, score) in enumerate(rows + [("Mean", mean)]):
+            w.writerow([i, ident] + [round(score[k], 5) if k in score else "" for k in keys])
+    return mean
+
+
+def test_all(config, save_volume=None, eval_pred=None):
     save_volume = getattr(config, "save_volume", False) if save_volume is None else save_volume
+    eval_pred = getattr(config, "eval_pred", False) if eval_pred is None else eval_pred
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -45,6 +68,7 @@ def test_all(config, save_volume=None):
     items = config.testlist or [{"cat_id": "synthetic", "shape_id": f"{i:04d}", "cam_id": i}
                                 for i in range(min(len(dataset), 2))]
     rank0 = (not dist.is_initialized()) or dist.get_rank() == 0
+    scores = {}                                          # cat -> [(ID, score)]
     for it in items:
         batch = dataset.get_testdata(it["cat_id"], it["shape_id"], it["cam_id"])
         t0 = time.time()
@@ -62,6 +86,20 @@ def test_all(config, save_volume=None):
             dt = time.time() - t0
             m.export(stem + "_pred.obj")
             print(f"  mesh: {len(m.vertices)} vertices, {len(m.faces)} faces in {dt * 1e3:.1f} ms -> {stem}_pred.obj")
+            if eval_pred:
+                gt = batch.get("gt_mesh")
+                if gt is None:
+                    print("  eval: skipped (the dataset gives no ground-truth mesh)")
+                    continue
+                t0 = time.time()
+                score = executor.eval(m, gt)
+                dt = time.time() - t0
+                scores.setdefault(it["cat_id"], []).append((f"{it['shape_id']}_{str(it['cam_id']).zfill(2)}", score))
+                print(f"  eval in {dt * 1e3:.1f} ms: " + ", ".join(f"{k}: {v:.5f}" for k, v in score.items()))
+    for cat, rows in scores.items():
+        mean = write_scores(out_dir + cat + ".csv", rows)
+        print(f"{config.exp_name} {cat} Mean ({len(rows)} items): " + ", ".join(f"{k}: {v:7.3f}" for k, v in mean.items())
+              + f" -> {out_dir}{cat}.csv")
     if dist.is_initialized():
         dist.destroy_process_group()
 
