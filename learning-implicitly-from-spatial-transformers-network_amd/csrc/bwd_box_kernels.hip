@@ -196,9 +196,7 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
       __syncthreads();                 // (one barrier per chunk: the other buffer was last read before the previous barrier)
       if (ci + 1 < nchunks) stage_load(ci + 1);
       const char* buf = smem + L::stage + (ci & 1) * L::stage_bytes;
-#ifdef LIST_ADJ_NO_MFMA            // ablation (wrong results; staging and barriers only): 0.239 -> 0.125 ms, 0.118 -> 0.070
-      if (sp.g.Kp < 0)
-#endif
+      // (the MFMAs left out, staging and barriers only: 16^3 level 0.239 -> 0.125 ms, 8^3 0.118 -> 0.070)
 #pragma unroll 1
       for (int ks = 0; ks < kAdjChunkPts / 4; ++ks) {
         const int plc = 4 * ks + q;                              // point of the chunk
@@ -254,13 +252,13 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
             const f16x8 a = __builtin_bit_cast(f16x8, (s16x8){a0[t][0], a0[t][1], a0[t][2], a0[t][3], a1[t][0], a1[t][1], a1[t][2], a1[t][3]});
             acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bhi[i], acc[i][t], 0, 0, 0);
           }
-#ifndef LIST_ADJ_HI_ONLY            // ablation (weights rounded to fp16): 16^3 level 0.253 -> 0.230 ms -- not worth the exactness
+          // the lo plane of the weights: rounding them to fp16 alone would save 16^3 level 0.253 -> 0.230 ms -- not
+          // worth the exactness
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
             const f16x8 a = __builtin_bit_cast(f16x8, (s16x8){a0[t][0], a0[t][1], a0[t][2], a0[t][3], a1[t][0], a1[t][1], a1[t][2], a1[t][3]});
             acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, blo[i], acc[i][t], 0, 0, 0);
           }
-#endif
         }
       }
     }
@@ -305,9 +303,7 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
     }
     __syncthreads();
     // flush: lanes over channel pairs, one box row per wave and pass -- 256 contiguous bytes per atomic instruction
-#ifdef LIST_ADJ_NO_FLUSH           // ablation (wrong results): 16^3 level 0.239 -> 0.154 ms, 8^3 0.118 -> 0.104
-    if (sp.g.Kp < 0)
-#endif
+    // (its share: 16^3 level 0.239 -> 0.154 ms, 8^3 0.118 -> 0.104 without it)
     {
       typedef _Float16 half2v __attribute__((ext_vector_type(2)));
       _Float16* base16 = img16 + (int64_t)rb_b * gv.image_stride;
@@ -329,14 +325,8 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
 }
 
 // a window level (stencil shorter than a voxel), fp16 dX, 128 channels, image scaled by `pk_scale`
-bool scatter_f32_diagnostic() {
-  static const bool on = [] { const char* e = getenv("LIST_SCATTER_F32"); return e && e[0] == '1'; }();
-  return on;
-}
-
 bool scatter_box_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, float pk_scale) {
-  static const bool off = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e && e[0] == '0' && e[1] == 0; }();
-  if (off || !sp.dx_f16 || gv.C != kAdjC || pk_scale != kAdjPkScale) return false;
+  if (!sp.dx_f16 || gv.C != kAdjC || pk_scale != kAdjPkScale) return false;
   if ((col_off % 8) != 0 || (sp.g.Kp % 8) != 0 || (gv.image_stride % 2) != 0) return false;
   if (gv.W > 255 || gv.H > 255 || gv.D > 255) return false;   // 8-bit coordinates in the run records
   return (sp.g.rows % kAdjPts) == 0;

@@ -290,8 +290,7 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box_split(ScatterParams 
 
 // a window level (stencil shorter than a voxel), fp32 dX, 128 channels
 bool scatter_box_split_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off) {
-  static const bool off = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e && e[0] == '0' && e[1] == 0; }();
-  if (off || sp.dx_f16 || gv.C != kSplC) return false;
+  if (sp.dx_f16 || gv.C != kSplC) return false;
   if ((col_off % 4) != 0 || (sp.g.Kp % 4) != 0) return false;
   if (gv.W > 255 || gv.H > 255 || gv.D > 255) return false;   // 8-bit coordinates in the run records
   return (sp.g.rows % kSplPts) == 0;

@@ -96,9 +96,9 @@ __device__ __forceinline__ s16x8 cat4(const s16x4& lo, const s16x4& hi) {
 // wave that wait on memory: capped at 194 registers (no scratch; the kernel itself is not slower, 0.78 ms) two of its
 // waves leave room for four of theirs per SIMD, and the fp16 backward takes 4.50 instead of 4.73 ms.
 // amdgpu_num_vgpr(112) is the LIMIT handed to the register allocator (architectural registers; the backend doubles it
-// for the unified file: at most 224); what the compiler then USES is 194, in all three instantiations the attribute
-// covers -- <1, 1> fp16, <1, 0> plain bf16, <3, 0> bf16x3 under LIST_TN_SHAPE=32 -- each with ScratchSize 0
-// (-Rpass-analysis=kernel-resource-usage, round 4).  The next lower limits that compile (96 and below) spill.
+// for the unified file: at most 224); what the compiler then USES is 194, in both instantiations -- <1, 1> fp16,
+// <1, 0> plain bf16 -- each with ScratchSize 0 (-Rpass-analysis=kernel-resource-usage, round 4; <3, 0> bf16x3 too).
+// The next lower limits that compile (96 and below) spill.
 template <int TERMS, int FP16>
 __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(112))) void k_gemm_tn(GemmTnParams p) {
   using P = TnPipe<TERMS>;
@@ -321,18 +321,9 @@ hipError_t launch_gemm_tn(const GemmTnParams& p, int terms, hipStream_t s) {
   // single-plane formats keep 32 x 32 x 16 (k_gemm_tn: 194 registers under its cap; the 16 x 16 x 32 form needs 246, is
   // 5 % slower on its own and leaves no room beside it); the split formats -- three MFMAs per product, one k32-step per
   // K-tile -- take 16 x 16 x 32 (212 registers; 0.1 ms ahead of the capped 32 x 32 x 16 form in the bf16x3 step).
-  // LIST_TN_SHAPE=16 / 32 forces one (A/B runs).
-  static const int forced = [] { const char* e = getenv("LIST_TN_SHAPE"); return e ? atoi(e) : 0; }();
-  const bool shape32 = forced == 32 || (forced != 16 && terms != 3);
-  if (shape32) {
-    if (p.fmt == FMT_FP16) hipLaunchKernelGGL((k_gemm_tn<1, 1>), grid, dim3(512), 0, s, p);
-    else if (terms == 3) hipLaunchKernelGGL((k_gemm_tn<3, 0>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((k_gemm_tn<1, 0>), grid, dim3(512), 0, s, p);
-  } else {
-    if (p.fmt == FMT_FP16) hipLaunchKernelGGL((k_gemm_tn16<1, 1>), grid, dim3(512), 0, s, p);
-    else if (terms == 3) hipLaunchKernelGGL((k_gemm_tn16<3, 0>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((k_gemm_tn16<1, 0>), grid, dim3(512), 0, s, p);
-  }
+  if (p.fmt == FMT_FP16) hipLaunchKernelGGL((k_gemm_tn<1, 1>), grid, dim3(512), 0, s, p);
+  else if (terms == 3) hipLaunchKernelGGL((k_gemm_tn16<3, 0>), grid, dim3(512), 0, s, p);
+  else hipLaunchKernelGGL((k_gemm_tn<1, 0>), grid, dim3(512), 0, s, p);
   return hipGetLastError();
 }
 

@@ -63,10 +63,8 @@ __device__ __forceinline__ void scatter_direct(const ScatterParams& sp, const Li
 // limit).  Beside other kernels (ListQueryGradArgs.aux_streams) a small grid is better for the whole: the
 // atomics of a CU fill its vector-memory queue, and every load of a neighbouring gather kernel waits behind
 // them (backward 5.92 ms with 512 workgroups, 5.57 ms with 128).
-#ifndef LIST_DIRECT_GRID_FORKED
-#define LIST_DIRECT_GRID_FORKED 128      // (re-measured in round 3 with dW0 capped at 194 registers: DESIGN 5b)
-#endif
-constexpr int kDirectGrid = 512, kDirectGridForked = LIST_DIRECT_GRID_FORKED;
+// (re-measured in round 3 with dW0 capped at 194 registers: DESIGN 5b)
+constexpr int kDirectGrid = 512, kDirectGridForked = 128;
 
 template <int C, int DXH>
 __global__ __launch_bounds__(256) void k_scatter_vox(ScatterParams sp, ListVoxLevel gv, int col_off, int nblocks) {
@@ -342,12 +340,6 @@ __global__ __launch_bounds__((C >= 128 ? C : 128)) void k_scatter_vox_win(Scatte
     // opens (the record itself is overwritten by the next chunk; DS operations of one wave execute in order)
     int* gro = grp_off[tid >> 6];
     auto add_group = [&]() {
-#ifdef LIST_WIN_NO_RMW             // ablation (wrong results): the read-add-writes of a group collapse into one
-      float gs = 0.f;
-#pragma unroll
-      for (int q = 0; q < 32; ++q) gs += Gacc[q];
-      mine[0] += gs;
-#else
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // (pairs with the release behind the gro[] stores)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {                  // two batches of 16 (addresses are distinct within the 32, or the dummy)
@@ -357,16 +349,11 @@ __global__ __launch_bounds__((C >= 128 ? C : 128)) void k_scatter_vox_win(Scatte
 #pragma unroll
         for (int q = 0; q < 16; ++q) mine[gro[16 * h + q]] = v[q] + Gacc[16 * h + q];
       }
-#endif
     };
 #pragma unroll 1
     for (int ch = 0; ch < r.count; ch += kSubPts) {
       __syncthreads();                               // previous chunk's records are consumed
-#ifndef LIST_WIN_NO_RECORDS        // ablation (wrong results): the per-point records are built once per workgroup only
       if (tid < kSubPts * 16) build_near(pts[r.first + ch + (tid >> 4)], W, H, D, r, C, nrec[tid >> 4], tid & 15);
-#else
-      if (tid < kSubPts * 16 && ri == 0 && ch == 0) build_near(pts[r.first + ch + (tid >> 4)], W, H, D, r, C, nrec[tid >> 4], tid & 15);
-#endif
       // my points of the chunk: every dX value is requested before the first use
       float gval[MYP][LIST_N_STENCIL];
 #pragma unroll
@@ -419,9 +406,6 @@ __global__ __launch_bounds__((C >= 128 ? C : 128)) void k_scatter_vox_win(Scatte
     }
     if (cur_cell != -2) add_group();
     __syncthreads();
-#ifdef LIST_WIN_NO_FLUSH           // ablation (wrong results): the window is never flushed
-    if (sp.g.Kp < 0)
-#endif
     if (DXH && img16) {
       _Float16* base16 = img16 + (int64_t)r.b * gv.image_stride;
       for (int i = tid; i < vol * (C / 2); i += T) {
@@ -694,8 +678,7 @@ static hipError_t gather_level(const ScatterParams& sp, const ListVoxLevel& gv, 
   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanThreads), 0, s, vb.sums, nb);
   hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(kScanThreads), 0, s, vb.bins, (int)n_vox, vb.sums);
   hipLaunchKernelGGL(k_vs_scatter<C>, gs, dim3(256), 0, s, sp, gv, vb.keys, vb.bins, (VoxSample*)vb.recs, col_off);
-  static const bool octets = [] { const char* e = getenv("LIST_VS_GATHER8"); return !(e && e[0] == '0'); }();
-  if (octets && (col_off % 8) == 0 && (sp.g.Kp % 8) == 0 && (reinterpret_cast<uintptr_t>(gv.data) & 15) == 0) {
+  if ((col_off % 8) == 0 && (sp.g.Kp % 8) == 0 && (reinterpret_cast<uintptr_t>(gv.data) & 15) == 0) {
     constexpr int VPB8 = 256 / (C / 8);
     const dim3 g8((unsigned)((n_vox + VPB8 - 1) / VPB8));
     if (sp.dx_f16)
@@ -735,6 +718,19 @@ __global__ __launch_bounds__(256) void k_scatter_vox1(ScatterParams sp, ListVoxL
   }
 }
 
+// LIST_SCATTER_BOX (environment, read once): which window levels take the matrix-core adjoint -- 0 neither, 1 the 8^3
+// level, 3 the 16^3 level, 2 both; unset (-1): the 16^3 level, and the 8^3 level when the call is not forked
+static int scatter_box_mode() {
+  static const int mode = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e ? atoi(e) : -1; }();
+  return mode;
+}
+// LIST_SCATTER_F32=1 (environment, read once; diagnostic for the tests): the window levels flush fp32 atomics (both
+// kernels) instead of packed halfs
+static bool scatter_f32_diagnostic() {
+  static const bool on = [] { const char* e = getenv("LIST_SCATTER_F32"); return e && e[0] == '1'; }();
+  return on;
+}
+
 template <int C>
 static hipError_t scatter_level(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s,
                                 _Float16* img16 = nullptr) {
@@ -748,7 +744,7 @@ static hipError_t scatter_level(const ScatterParams& sp, const ListVoxLevel& gv,
         // fp16, 128 channels: on the matrix cores (k_scatter_vox_box) -- alone 0.28 -> 0.12 ms; beside the other streams of
         // the forked backward the VALU kernel is the better neighbour (2 waves of 199 registers per workgroup against 4 of
         // 243: step +0.05 ms with the matrix-core form), so forked calls keep it unless LIST_SCATTER_BOX=2
-        static const int box_mode = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e ? atoi(e) : -1; }();
+        const int box_mode = scatter_box_mode();
         const bool box8 = box_mode < 0 ? !sp.forked : (box_mode == 1 || box_mode == 2);
         if (box8 && (img16 || scatter_f32_diagnostic()) && scatter_box_eligible(sp, gv, col_off, kWinPkScale))
           return launch_scatter_vox_box(sp, gv, col_off, img16, s);
@@ -758,7 +754,7 @@ static hipError_t scatter_level(const ScatterParams& sp, const ListVoxLevel& gv,
         else hipLaunchKernelGGL((k_scatter_vox_win<C, 0, 9216>), grid, dim3(T), 0, s, sp, gv, col_off, (_Float16*)nullptr);
       } else {
         // 16^3: the same kernel with runs of <= 128 box rows: alone 0.52 -> 0.24 ms, forked step 6.63 -> 6.29 ms
-        static const int box_mode = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e ? atoi(e) : -1; }();
+        const int box_mode = scatter_box_mode();
         const bool box16 = box_mode < 0 || box_mode == 2 || box_mode == 3;
         if (box16 && (img16 || scatter_f32_diagnostic()) && scatter_box_eligible(sp, gv, col_off, kWinPkScale))
           return launch_scatter_vox_box(sp, gv, col_off, img16, s);
@@ -796,7 +792,6 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
                                          (double)sp.g.n_valid * LIST_N_STENCIL >= kVoxGatherMinDensity * (double)n_vox);
     if (vb.bins && dense && n_vox <= kVoxGatherMaxBins && (gv.C == 16 || gv.C == 32 || gv.C == 64 ||
                                                                            gv.C == 128 || gv.C == 256)) {
-      if (bwd_knockout() & 16) continue;
       switch (gv.C) {
         case 16: e = gather_level<16>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
         case 32: e = gather_level<32>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
@@ -807,7 +802,6 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
       if (e != hipSuccess) return e;
       continue;
     }
-    if (window_level ? (bwd_knockout() & (n_win_seen == 0 ? 4 : 8)) : (bwd_knockout() & 2)) { if (window_level) ++n_win_seen; continue; }
     // the first window level shares its stream with dW0; the second one has a stream to itself (st.window2: the
     // library's own side stream when the backward is forked, else the caller's).  With both behind the (contended) 2-ms
     // dW0 the window stream ended 0.4 ms after the other two (forked backward 5.16 -> 4.98 ms with the second one behind
@@ -818,7 +812,6 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
     // gathers: +0.08 / +0.4 ms, profiles/r04b_box_adjoint.txt)
     hipStream_t s = st.direct;
     if (window_level && vb.mode != 2) { s = n_win_seen == 0 ? st.window : st.window2; ++n_win_seen; }
-#ifndef LIST_BWD_NO_PK_ATOMICS
     // packed-half atomics (see k_scatter_vox_h2): fp16 operands, automatic form choice, C = 32 or a non-window C = 64
     // level, and the level's fp16 image fits the scratch the caller set aside
     {
@@ -843,8 +836,6 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
         continue;
       }
     }
-#endif
-#ifndef LIST_BWD_NO_PK_ATOMICS
     // window levels, fp16 operands: packed-half flush into the level's fp16 image (its own scratch slot: the window
     // levels run beside the direct ones), then one pass to fp32
     if (window_level && sp.dx_f16 && vb.mode == 0 && (gv.C == 64 || gv.C == 128 || gv.C == 256) && vb.h16w && !scatter_f32_diagnostic()) {
@@ -871,7 +862,6 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
         continue;
       }
     }
-#endif
     e = hipMemsetAsync((void*)gv.data, 0, (size_t)B * gv.image_stride * sizeof(float), s);
     if (e != hipSuccess) return e;
     if (gv.C == 1) {
@@ -1213,11 +1203,8 @@ struct TransPt { int64_t o00; int sx, sy; int row, b, valid; float wx0, wx1, wy0
 // grid = rows/64, block = 256: the first 64 threads project the workgroup's points (pixel order), then
 // the workgroup walks them with lanes over channel octets (16-B loads of the four taps and of dX), a
 // whole number of points per pass; wave shuffles + LDS reduce the two coordinate derivatives per point.
-#ifndef LIST_TRANS_VGPR_ATTR
-#define LIST_TRANS_VGPR_ATTR
-#endif
 template <int F16, int DXH>
-__global__ __launch_bounds__(256) LIST_TRANS_VGPR_ATTR void k_trans_grad(ScatterParams sp, const void* __restrict__ img_map,
+__global__ __launch_bounds__(256) void k_trans_grad(ScatterParams sp, const void* __restrict__ img_map,
                                                     const float* __restrict__ trans_mat, int ms, int Ct,
                                                     float clamp_hi, int img_off, float* __restrict__ grad_T) {
   __shared__ TransPt tp[kGatherRows];
@@ -1451,10 +1438,7 @@ hipError_t launch_img_grad(const ScatterParams& sp, const FeatLayout& L, const L
 //   2. out[c][xs] = sum_ox wx(ox, xs) R[ox][c]          R through LDS, per-xs tap lists in CSR form;
 //   3. the [64][W] tile turns through LDS so the NCHW writes run along x.
 constexpr int kAdjMaxMs = 320;             // largest supported map_size
-#ifndef LIST_ADJ_CG
-#define LIST_ADJ_CG 32
-#endif
-constexpr int kAdjCg = LIST_ADJ_CG;        // channels per workgroup (A/B: 64 = 72 KB of LDS, two workgroups per CU)
+constexpr int kAdjCg = 32;                 // channels per workgroup (A/B: 64 = 72 KB of LDS, two workgroups per CU)
 constexpr int kAdjXl = 256 / (kAdjCg / 4); // x lanes of phase 1 (a lane owns 4 channels)
 constexpr int kAdjCols = (kAdjMaxMs + kAdjXl - 1) / kAdjXl;
 

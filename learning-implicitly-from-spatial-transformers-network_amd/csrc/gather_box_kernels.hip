@@ -35,44 +35,9 @@ namespace list {
 constexpr int kBoxPts = 64;                                  // points per workgroup
 constexpr int kBoxSamples = kBoxPts * LIST_N_STENCIL;        // 448
 constexpr int kBoxMaxKeys = 512;                             // window keys a run may have
-#ifndef LIST_BOX_NB
-#define LIST_BOX_NB 2                                        // tiles per turn of a wave
-#endif
-#ifndef LIST_BOX_ROWS_BIG
-#ifdef LIST_BOX_XPOSE
-#define LIST_BOX_ROWS_BIG 224                                // LDS box rows, levels wider than 8 voxels (2 workgroups per CU)
-#else
-#define LIST_BOX_ROWS_BIG 256
-#endif
-#endif
-#ifndef LIST_BOX_ROWS_SMALL
-#ifdef LIST_BOX_XPOSE
-#define LIST_BOX_ROWS_SMALL 120                              // (3 workgroups per CU)
-#else
-#define LIST_BOX_ROWS_SMALL 128
-#endif
-#endif
-
-// diagnostic build only (-DLIST_BOX_STAMPS): cycles per phase, summed over the workgroups by wave 0 / lane 0 into a
-// buffer of their own (list_debug_box_stamps); no stamp executes in the shipped kernel
-#ifdef LIST_BOX_STAMPS
-__device__ unsigned long long g_box_stamps[2][4096][16];      // [small / big box][workgroup][slot]: own words, no atomics
-#define BOX_STAMP(slot)                                                                                     \
-  do {                                                                                                      \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    unsigned long long t_;                                                                                  \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                             \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    if (tid == 0) st_[slot] += t_ - t_prev_;                                                                \
-    t_prev_ = t_;                                                                                           \
-  } while (0)
-#define BOX_STAMP_INIT()                                                                                    \
-  unsigned long long t_prev_, st_[16] = {0};                                                                \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_prev_)::"memory")
-#else
-#define BOX_STAMP(slot) do {} while (0)
-#define BOX_STAMP_INIT() do {} while (0)
-#endif
+constexpr int kBoxNb = 2;                                    // tiles per turn of a wave
+constexpr int kBoxRowsBig = 256;                             // LDS box rows, levels wider than 8 voxels
+constexpr int kBoxRowsSmall = 128;
 
 template <int C, int MAXROWS> struct BoxLds {
   static constexpr int kRowBytes = 2 * C;
@@ -84,12 +49,7 @@ template <int C, int MAXROWS> struct BoxLds {
   static constexpr int sorted = tileinfo + kBoxSamples * 4;              // short [448]: sample ids in key order
   static constexpr int pbox = sorted + kBoxSamples * 2;                  // int [64][4]: tap range per axis, image
   static constexpr int misc = pbox + kBoxPts * 16;                       // int [8]: tile count
-#ifdef LIST_BOX_XPOSE
-  static constexpr int xpose = misc + 64;                                // 4 waves x [8 samples][256 B]: store staging
-  static constexpr int total = xpose + 4 * 8 * kRowBytes;
-#else
   static constexpr int total = misc + 64;
-#endif
 };
 
 // grid = rows / 64, block = 256
@@ -118,7 +78,6 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
   const int64_t row0 = (int64_t)blk * kBoxPts;
   const int W = lv.W, H = lv.H, D = lv.D;
 
-  BOX_STAMP_INIT();
   // ---- 1a. waves 0..2: axis `wave` of the 64 points -- weight records of the centre / -d / +d coordinate -----------
   if (wave < 3) {
     const Pt p = load_point(g, (int)row0 + lane);
@@ -138,7 +97,6 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
   } else {
     for (int k = lane; k < kBoxMaxKeys; k += 64) keyinfo[k] = 0;
   }
-  BOX_STAMP(0);
   __syncthreads();
   // ---- 1b. wave 0: aligned power-of-two runs whose box fits (segment tree over the tap ranges) ----------------------
   if (wave == 0) {
@@ -170,9 +128,7 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
       runs[lane] = rb;
     }
   }
-  BOX_STAMP(1);
   __syncthreads();
-  BOX_STAMP(2);
 
   const unsigned short* __restrict__ vsrc = (const unsigned short*)lv.data;
   unsigned short* __restrict__ xh = g.x_hi;
@@ -241,7 +197,6 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
       my_slot[i] = atomicAdd(&keyinfo[key], 1);
     }
     __syncthreads();
-    BOX_STAMP(3);
 
     // ---- 2c. wave 0: exclusive scan over the keys -> sample offsets, tiles; meanwhile the box lands -----------------
     if (wave == 0) {
@@ -284,20 +239,15 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
       *(uint4*)(smem + L::box + (bdst[i] & 0x3fffffff)) = w;
     }
     __syncthreads();
-    BOX_STAMP(4);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       if (my_key[i] >= 0) sorted[keyinfo[my_key[i]] + my_slot[i]] = (short)my_sid[i];
     __syncthreads();
-    BOX_STAMP(5);
     for (int k = tid; k < nkeys; k += 256) keyinfo[k] = 0;    // counters of the next run (nothing below reads them)
 
     // ---- 2d. tiles: <= 16 samples of one window; two tiles per turn (independent chains of LDS look-ups) -----------
     const int ntiles = uni(misc[0]);
-    constexpr int NB = LIST_BOX_NB;
-#ifdef LIST_BOX_NO_TILES
-    if (g.Kp < 0)
-#endif
+    constexpr int NB = kBoxNb;
 #pragma unroll 1
     for (int T = wave; T < ntiles; T += 4 * NB) {
       unsigned bh[NB][4], bl[NB][4];
@@ -376,38 +326,6 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
         // D^T: column = sample (lane & 15), rows 4 q + reg of tile t = channels 32 (t >> 1) + 8 q + 4 (t & 1) + reg.
         // Plain stores: the four lanes of a sample cover 64 B per instruction and the partial lines merge in L2
         // (non-temporal stores of such pieces took the kernel from 0.085 to 0.30 ms)
-#ifdef LIST_BOX_XPOSE
-        {
-          // whole rows per store instruction: the tile turns through a wave-private LDS image, 8 samples at a time
-          // ([sample][16-B chunk ^ sample]: conflict-free both ways; DS operations of one wave execute in order), then
-          // every 16 lanes hold one sample's 256 B -> non-temporal stores of full rows like the scalar kernels'
-          typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-          char* tw = smem + L::xpose + wave * (8 * RB);
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) {
-            if ((col >> 3) == hh) {
-#pragma unroll
-              for (int u = 0; u < NT / 2; ++u) {
-                const uint2 lo = half4_inrange(make_float4(acc[2 * u][0], acc[2 * u][1], acc[2 * u][2], acc[2 * u][3]));
-                const uint2 hi = half4_inrange(make_float4(acc[2 * u + 1][0], acc[2 * u + 1][1], acc[2 * u + 1][2], acc[2 * u + 1][3]));
-                *(uint4*)(tw + (col & 7) * RB + (((4 * u + q) ^ (col & 7)) << 4)) = make_uint4(lo.x, lo.y, hi.x, hi.y);
-              }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // lanes read what other lanes of the wave stored
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int k2 = 0; k2 < 2; ++k2) {
-              const int r8 = 4 * k2 + (lane >> 4), chunk = lane & 15;
-              const uint4 v = *(const uint4*)(tw + r8 * RB + ((chunk ^ r8) << 4));
-              const int sd = __shfl(sid[b], 8 * hh + r8);
-              if (sd >= 0) {
-                unsigned short* dst = xh + (row0 + (sd >> 3)) * g.Kp + col_off + (sd & 7) * C + 8 * chunk;
-                __builtin_nontemporal_store((u32x4){v.x, v.y, v.z, v.w}, (u32x4*)dst);
-              }
-            }
-          }
-        }
-#else
         if (sid[b] >= 0) {
           const int pt = sid[b] >> 3, j = sid[b] & 7;
           unsigned short* dst = xh + (row0 + pt) * g.Kp + col_off + j * C + 8 * q;
@@ -416,37 +334,14 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
           for (int u = 0; u < NT / 2; ++u) {
             const uint2 lo = half4_inrange(make_float4(acc[2 * u][0], acc[2 * u][1], acc[2 * u][2], acc[2 * u][3]));
             const uint2 hi = half4_inrange(make_float4(acc[2 * u + 1][0], acc[2 * u + 1][1], acc[2 * u + 1][2], acc[2 * u + 1][3]));
-#if defined(LIST_BOX_NO_STORE)
-            asm volatile("" :: "v"(lo.x), "v"(lo.y), "v"(hi.x), "v"(hi.y));
-#elif defined(LIST_BOX_NT_STORE)
-            __builtin_nontemporal_store((u32x4){lo.x, lo.y, hi.x, hi.y}, (u32x4*)(dst + 32 * u));
-#elif defined(LIST_BOX_SC1_STORE)
-            {
-              const u32x4 val = {lo.x, lo.y, hi.x, hi.y};
-              asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst + 32 * u), "v"(val) : "memory");
-            }
-#else
             *(u32x4*)(dst + 32 * u) = (u32x4){lo.x, lo.y, hi.x, hi.y};
-#endif
           }
         }
-#endif
       }
     }
     first += count;
-    BOX_STAMP(6);
     if (first < kBoxPts) __syncthreads();                     // the next run overwrites the box and the lists
-    BOX_STAMP(7);
-#ifdef LIST_BOX_STAMPS
-    if (tid == 0) { st_[8] += 1; st_[9] += ntiles; st_[10] += rows; st_[11] += nkeys; }
-#endif
   }
-#ifdef LIST_BOX_STAMPS
-  if (tid == 0 && blockIdx.x < 4096) {
-    st_[12] = 1;
-    for (int i = 0; i < 16; ++i) g_box_stamps[MAXROWS == LIST_BOX_ROWS_BIG ? 1 : 0][blockIdx.x][i] = st_[i];
-  }
-#endif
 }
 
 // near level with fp16 maps and an fp16 feature matrix; false: not taken (the caller falls back to k_gather_vox_near)
@@ -463,18 +358,10 @@ hipError_t launch_gather_vox_box(const GatherParams& g, const ListVoxLevel& lv, 
   // the 8^3 level's boxes are small: a 128-row box leaves room for three workgroups per CU
   const int big = lv.W > lv.H ? (lv.W > lv.D ? lv.W : lv.D) : (lv.H > lv.D ? lv.H : lv.D);
   if (big > 8)
-    LIST_LAUNCH((k_gather_vox_box<128, LIST_BOX_ROWS_BIG>), dim3(g.rows / kBoxPts), dim3(256), 0, s, order, g, lv, col_off);
+    LIST_LAUNCH((k_gather_vox_box<128, kBoxRowsBig>), dim3(g.rows / kBoxPts), dim3(256), 0, s, order, g, lv, col_off);
   else
-    LIST_LAUNCH((k_gather_vox_box<128, LIST_BOX_ROWS_SMALL>), dim3(g.rows / kBoxPts), dim3(256), 0, s, order, g, lv, col_off);
+    LIST_LAUNCH((k_gather_vox_box<128, kBoxRowsSmall>), dim3(g.rows / kBoxPts), dim3(256), 0, s, order, g, lv, col_off);
   return hipGetLastError();
 }
-
-#ifdef LIST_BOX_STAMPS
-extern "C" int list_debug_box_stamps(unsigned long long* out, int reset) {     // out: [2][4096][16]
-  (void)reset;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_box_stamps), sizeof(g_box_stamps)) != hipSuccess) return -1;
-  return 0;
-}
-#endif
 
 }  // namespace list

@@ -176,9 +176,7 @@ template <int C, int V> struct VoxGeom {
   static constexpr int RB = 4 * PW * ITERS;                         // rows per workgroup: 64, 128 or 256
 };
 
-#ifndef LIST_VOX_WAVES
-#define LIST_VOX_WAVES 1
-#endif
+constexpr int kVoxWaves = 1;                                        // minimum waves per EU of k_gather_vox
 // TAIL: the scalar level of the same grid, xyz and the zero padding ride along (TailRide above; k_gather_tail's work)
 struct TailArgs { const float* l0; int64_t l0_stride; int l0_off, xyz_off, F; int* nan_tiles; };
 
@@ -186,7 +184,7 @@ template <int FMT>
 __device__ __forceinline__ void write_xyz_and_pad(const GatherParams& g, const Pt& p, int64_t ro, int xyz_off, int F);
 
 template <int C, int FMT, int F16, int TAIL = 0>
-__global__ __launch_bounds__(256, LIST_VOX_WAVES) void k_gather_vox(GatherParams g, ListVoxLevel lv, int col_off, TailArgs ta) {
+__global__ __launch_bounds__(256, kVoxWaves) void k_gather_vox(GatherParams g, ListVoxLevel lv, int col_off, TailArgs ta) {
   using M = MapT<F16>;
   using G = VoxGeom<C, M::V>;
   __shared__ Pt pts[G::RB];
@@ -446,12 +444,8 @@ __global__ __launch_bounds__(256) void k_sort_hist(GatherParams g, SortParams sp
     keys_m[i] = k.morton;
     if (sp.pixel) keys_p[i] = k.pixel;
   }
-#ifdef LIST_SORT_PLAIN_ATOMICS      // A/B: one atomic per point
-  if (active) { atomicAdd(&bins_m[k.morton], 1); if (sp.pixel) atomicAdd(&bins_p[k.pixel], 1); }
-#else
   wave_grouped_add(bins_m, k.morton, active, false);
   if (sp.pixel) wave_grouped_add(bins_p, k.pixel, active, false);
-#endif
 }
 
 // Exclusive scan of the counters, one workgroup per (order, image slot).  The number of points of
@@ -492,22 +486,12 @@ __global__ __launch_bounds__(256) void k_sort_scatter(int n_valid, const int* __
                                                       int* __restrict__ row_of, int* __restrict__ order_img) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool active = i < n_valid;
-#ifdef LIST_SORT_PLAIN_ATOMICS
-  if (!active) return;
-  const int pos = atomicAdd(&bins_m[keys_m[i]], 1);
-  order[pos] = i;
-  if (order_img) {
-    row_of[i] = pos;
-    order_img[atomicAdd(&bins_p[keys_p[i]], 1)] = i;
-  }
-#else
   const int pos = wave_grouped_add(bins_m, active ? keys_m[i] : 0, active, true);
   if (active) order[pos] = i;
   if (order_img) {                                   // (uniform: a kernel argument)
     const int pp = wave_grouped_add(bins_p, active ? keys_p[i] : 0, active, true);
     if (active) { row_of[i] = pos; order_img[pp] = i; }
   }
-#endif
 }
 
 hipError_t launch_sort_points(const GatherParams& g, const ListQueryArgs& a, const SortBuffers& sb,
@@ -645,11 +629,7 @@ __global__ __launch_bounds__(256) void k_gather_img(GatherParams g, const void* 
         // the perceptual block of a row is 2 KB of whole, line-aligned lines written once: non-temporal (round 4, two
         // interleaved pairs on one device: this kernel 0.244 -> 0.235 ms, gather group 0.850 -> 0.828, step -0.02 ms;
         // the 32 ... 256-B pieces of the voxel gathers keep the plain stores that merge in L2, list_common.h x_store)
-#ifdef LIST_IMG_PLAIN_STORES
-        store_feats<FMT, M::V>(xh, xl, (int64_t)a.row * g.Kp + col_off + q * M::V, r, a.valid != 0);
-#else
         store_feats<FMT, M::V, true>(xh, xl, (int64_t)a.row * g.Kp + col_off + q * M::V, r, a.valid != 0);
-#endif
       }
     }
   }
@@ -887,12 +867,6 @@ static hipError_t launch_vox_level(const GatherParams& g, const ListVoxLevel& lv
   return launch_vox_level_t<C, FMT, 0>(g, lv, col_off, s, order, ride);
 }
 
-#ifndef LIST_GATHER_SEQ
-#define LIST_GATHER_SEQ 123I45T
-#endif
-#define LIST_STR2(x) #x
-#define LIST_STR(x) LIST_STR2(x)
-
 template <int FMT>
 static hipError_t launch_gather_fmt(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a,
                                     int* nan_tiles, hipStream_t s, bool skip_img) {
@@ -993,18 +967,20 @@ static hipError_t launch_gather_fmt(const GatherParams& g, const FeatLayout& L, 
   // level, I = 2-D gather, T = tail; whatever the sequence does not name follows in level order).  Five sequences
   // measured within 1 % of each other in round 2; the coarse levels first, then the 2-D gather, then the HBM-bound
   // fine levels was the best.  Round 3 (coarse levels on the matrix cores, gather_box_kernels.hip), eleven sequences on
-  // one device (tools/ab_gather.sh): with the coarse levels LAST the group takes 0.79-0.83 instead of 0.85-0.87 ms and
-  // fc_0 behind it 0.50-0.53 instead of 0.48 ms -- group + fc_0 = 1.34-1.35 ms whatever the order (the X lines the
-  // gathers leave dirty in the L2s drain into whatever runs next), the step 2.04-2.10 ms.  Kept: the round-2 order
+  // one device (tools/ab_gather.sh, script removed; see git history before this change): with the coarse levels LAST
+  // the group takes 0.79-0.83 instead of 0.85-0.87 ms and fc_0 behind it 0.50-0.53 instead of 0.48 ms -- group + fc_0
+  // = 1.34-1.35 ms whatever the order (the X lines the gathers leave dirty in the L2s drain into whatever runs next),
+  // the step 2.04-2.10 ms.  Kept: the round-2 order
   // Round 4b: with the 2-D sample inside fc_0 and fc_0 short of its projected K-tiles (fp16 inference forwards) the
   // balance moved: the fine levels FIRST and the matrix-core levels last, 123I45T, takes the fp16 step from 1.944 / 1.951
-  // to 1.930 / 1.922 ms (group -0.05, fc_0 +0.02; two interleaved repetitions, tools/r4b_seq_ab.sh); bf16x3 and the training
-  // step inside their noise, plain bf16 +0.02.  Now the default.
+  // to 1.930 / 1.922 ms (group -0.05, fc_0 +0.02; two interleaved repetitions, tools/r4b_seq_ab.sh, script removed;
+  // see git history before this change); bf16x3 and the training step inside their noise, plain bf16 +0.02.  Now the
+  // default.
   // (Round 4, measured and dropped: the seven gathers spread over two to four QUEUES -- side streams forked and joined
   // around this group -- run side by side (group 0.85 -> 0.79 ms) but every launch around them pays for the fork / join
   // (sort, fc_0, tail, the preps of the next step): step 2.08 -> 2.08 ... 2.18 ms over five assignments.)
   bool done[LIST_N_VOX_LEVELS + 2] = {false};
-  for (const char* c = LIST_STR(LIST_GATHER_SEQ); ; ++c) {
+  for (const char* c = "123I45T"; ; ++c) {
     const bool rest = *c == 0;
     for (int l = 0; l < LIST_N_VOX_LEVELS + 2; ++l) {
       const bool named = l < LIST_N_VOX_LEVELS ? *c == '0' + l : *c == (l == LIST_N_VOX_LEVELS ? 'I' : 'T');

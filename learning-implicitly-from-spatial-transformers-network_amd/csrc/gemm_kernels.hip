@@ -73,14 +73,10 @@ __device__ __forceinline__ void stage_tiles(const GemmParams& p, char* sbase, in
     const int64_t aoff = (int64_t)(m0 + row) * ld + kbyte + chunk * 16;
     const int64_t woff = (int64_t)(n0 + row) * ld + kbyte + chunk * 16;
     char* l = sbase + piece * 1024;
-#ifndef LIST_GEMM_NO_A
     glds16(p.a_hi + aoff, l);
     if (TERMS == 3) glds16(p.a_lo + aoff, l + P::kPlaneBytes);
-#endif
-#ifndef LIST_GEMM_NO_W
     glds16(p.w_hi + woff, l + P::kWOff);
     if (TERMS == 3) glds16(p.w_lo + woff, l + P::kWOff + P::kPlaneBytes);
-#endif
   }
 }
 
@@ -301,11 +297,9 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt(GemmParams p) {
     else if (younger == 1) wait_vmcnt<P::kLoadsPerStage>();
     else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
-#ifndef LIST_GEMM_NO_LOAD
     if (t + P::kAhead < nk)
       stage_tiles<TERMS>(p, smem + ((t + P::kAhead) % P::kStages) * P::kStageBytes, m0, n0,
                          (t + P::kAhead) * P::kRowBytes, wave, lane);
-#endif
     const char* cur = smem + (t % P::kStages) * P::kStageBytes;
     // Register double-buffered fragments: the ds_reads of k16-step s2+1 are issued ahead of the MFMAs
     // of step s2 (written as one buffer, hipcc reuses four fragment registers and exposes an
@@ -327,9 +321,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt(GemmParams p) {
           wl[buf][j] = *(const bf16x8*)(cur + P::kWOff + P::kPlaneBytes + w_row_off + j * 32 * P::kRowBytes + coff);
       }
     };
-#ifdef LIST_GEMM_NO_FRAGS
-    continue;        // ablation: LDS-DMA stream + barrier only
-#endif
     load_frags(0, 0);
 #pragma unroll
     for (int s2 = 0; s2 < NS; ++s2) {
@@ -343,11 +334,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt(GemmParams p) {
             acc[i][j] = mfma<0>(al[b][i], wh[b][j], acc[i][j]);
             acc[i][j] = mfma<0>(ah[b][i], wl[b][j], acc[i][j]);
           }
-#ifdef LIST_GEMM_NO_MFMA
-          asm volatile("" ::"v"(ah[b][i]), "v"(wh[b][j]));
-#else
           acc[i][j] = mfma<FP16>(ah[b][i], wh[b][j], acc[i][j]);
-#endif
         }
     }
   }
@@ -571,7 +558,7 @@ __device__ __forceinline__ void gemm_epilogue16(const GemmParams& p, f32x4v (&ac
 // ---- ping-pong schedule (single-plane operands, BK = 64) -----------------------------------------------------------
 // Same tile, LDS image, swizzle and epilogues as the plain loops; a different schedule, after the guide's 256^2 8-phase
 // template.  A K-tile is four phases, one 64 x 32 quadrant of the wave's 128 x 64 outputs each (over K = 64: 16 MFMAs
-// of 16x16x32, or 8 of 32x32x16 with -DLIST_PP_SHAPE32):
+// of 16x16x32 -- the shape every launch takes --, or 8 of 32x32x16 with S16 = false):
 //   p0: read A(first 64 rows), W(first 32 cols) -> q(0,0)   p1: read W(second) -> q(0,1)   p2: read A(second) -> q(1,1)
 //   p3: -> q(1,0)
 // Every phase is [READ: ds_reads + ONE quarter of the next K-tile's LDS-DMA staging | s_barrier | MFMAs | s_barrier],
@@ -595,25 +582,8 @@ __device__ __forceinline__ void gemm_epilogue16(const GemmParams& p, f32x4v (&ac
 __device__ __forceinline__ int a_quarter_row(int q, int half) { return (q >> 3) * 128 + half * 64 + (q & 7) * 8; }
 __device__ __forceinline__ int w_quarter_row(int q, int half) { return (q >> 2) * 64 + half * 32 + (q & 3) * 8; }
 
-#ifndef LIST_PP_LEAD
-#define LIST_PP_LEAD 4
-#endif
-constexpr int kLead = LIST_PP_LEAD;      // phases between the issue of a staging quarter and the phase that owns it (4..6)
-#ifdef LIST_PP_SHAPE32
-constexpr bool kPpShape16 = false;
-#else
-constexpr bool kPpShape16 = true;
-#endif
-template <int P> __device__ __forceinline__ void pp_prio() {
-#ifndef LIST_PP_NO_SETPRIO
-  __builtin_amdgcn_s_setprio(P);
-#endif
-}
-__device__ __forceinline__ void pp_fence() {
-#ifndef LIST_PP_NO_FENCE
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-}
+constexpr int kLead = 4;                 // phases between the issue of a staging quarter and the phase that owns it (4..6)
+constexpr int kPpMinK = 512;             // K from which launches take the ping-pong schedule (launch_one)
 
 // X3 (split formats, 16x16x32 shape only): the operands hold hi and lo halfs interleaved in 64-B blocks (xi_off), so a
 // 128-B LDS row is [32 hi | 32 lo] of a K-tile of 32 columns -- the staging, the LDS image and the fragment reads are
@@ -693,17 +663,9 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
       const int row0 = is_a ? a_quarter_row(q, quarter == 3) : w_quarter_row(q, quarter == 2);
       const int row = row0 + lane / 8;
       const int chunk = (lane % 8) ^ P::swz(row);
-#ifdef LIST_PP_A_RESIDENT     // ablation (wrong results): every tile stages the A rows of the first M-tile -- no HBM stream for A,
-      // the LDS-DMA volume of a 128 x 512 tile that streams W twice and produces its A on chip
-      const char* g = (is_a ? A + (int64_t)min(row, a_last) * lda : Wt + (int64_t)(n0 + row) * ldw) + kbyte + chunk * 16;
-#else
       const char* g = (is_a ? A + (int64_t)min(m0 + row, a_last) * lda : Wt + (int64_t)(n0 + row) * ldw) + kbyte + chunk * 16;
-#endif
-#ifndef LIST_PP_A_DEFAULT_POLICY
       if (EPI == EPI_RELU_SPLIT && is_a) glds16_nt(g, sbase + row0 * P::kRowBytes);
-      else
-#endif
-      glds16(g, sbase + (is_a ? 0 : P::kWOff) + row0 * P::kRowBytes);
+      else glds16(g, sbase + (is_a ? 0 : P::kWOff) + row0 * P::kRowBytes);
     }
   };
   auto frag = [&](const char* cur, int plane_off, int row_off, int blk, int ks) -> bf16x8 {
@@ -747,17 +709,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
       // quarter g = k + kLead of the sequence (k = 4 t + ph)
       const int tt = t + (ph + kLead) / 4;
       const int sq = (ph + kLead) & 3;
-#ifdef LIST_PP_NO_LOAD        // ablation: only the prologue's quarters are ever staged (real data, no load stream)
-      if (false) {
-#else
       if (STEADY) {
-#endif
         stage_quarter(smem + (tt & 1) * P::kStageBytes, ktb(tt), sq);
         wait_vmcnt<2 * (kLead - 2)>();     // my loads of every quarter up to k + 2 have landed
       } else {
-#ifndef LIST_PP_NO_LOAD
         if (tt < nk) stage_quarter(smem + (tt & 1) * P::kStageBytes, ktb(tt), sq);
-#endif
         const int beyond = last_quarter - (4 * t + ph + 2);        // quarters issued beyond k + 2
         if (beyond >= 4) wait_vmcnt<2 * (kLead - 2 < 4 ? kLead - 2 : 4)>();
         else if (beyond == 3) wait_vmcnt<2 * (kLead - 2 < 3 ? kLead - 2 : 3)>();
@@ -765,12 +721,12 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
         else if (beyond == 1) wait_vmcnt<2>();
         else wait_vmcnt<0>();
       }
-      pp_fence();
+      __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       // ---- MFMA section: one 64 x 32 quadrant over the whole K-tile, pinned between its two barriers
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      pp_fence();
-      pp_prio<1>();
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
       const int ih = ph < 2 ? 0 : 1, jh = (ph == 0 || ph == 3) ? 0 : 1;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
@@ -778,9 +734,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
         for (int bi = 0; bi < HA; ++bi)
 #pragma unroll
           for (int bj = 0; bj < HW; ++bj) {
-#ifdef LIST_PP_NO_MFMA       // ablation: operands stay live, no MFMA issued
-            asm volatile("" ::"v"(a[bi][ks]), "v"(w[jh][bj][ks]));
-#else
             auto& c = acc[ih * HA + bi][jh * HW + bj];
             if constexpr (X3 != 0) {
               if (ks == 0) {                 // [0] = hi halfs, [1] = lo halfs of the same 32 columns
@@ -792,12 +745,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
               }
             } else if constexpr (S16) c = mfma16<FP16>(a[bi][ks], w[jh][bj][ks], c);
             else c = mfma<FP16>(a[bi][ks], w[jh][bj][ks], c);
-#endif
           }
-      pp_prio<0>();
-      pp_fence();
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
-      pp_fence();
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
   int t = 0;
@@ -1075,38 +1027,30 @@ static hipError_t launch_one(const GemmParams& p, hipStream_t s) {
   if constexpr (EPI == EPI_RELU_DOT)
     hipLaunchKernelGGL((k_gemm_nt16<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
   else {
-#ifndef LIST_GEMM_NO_PINGPONG
     // the ping-pong schedule pays from 8 K-tiles on (fc_0: 57 K-tiles; fc_1 0.088 -> 0.081 ms and dX 0.82 -> 0.78 ms at
     // 8); at 4 K-tiles (dH) its prologue and stagger cancel the gain and the plain 2-stage loop stays.  plain_loop
     // (diagnostic) takes the plain loop of the SAME MFMA shape: bit-identical results, which makes it the schedule's
     // race detector.
-#ifndef LIST_PP_MIN_K
-#define LIST_PP_MIN_K 512
-#endif
-    if constexpr (TERMS == 1 && (EPI == EPI_RELU_SPLIT || EPI == EPI_F32 || (kPpShape16 && (EPI == EPI_DX || EPI == EPI_MASK_SPLIT)))) {
-      if (p.K >= LIST_PP_MIN_K || need_pp) {
-        if (!p.plain_loop) hipLaunchKernelGGL((k_gemm_nt_pp<EPI, FP16, kPpShape16>), dim3(ntiles), dim3(512), 0, s, p);
-        else if (kPpShape16) hipLaunchKernelGGL((k_gemm_nt16<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((k_gemm_nt<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
+    if constexpr (TERMS == 1 && (EPI == EPI_RELU_SPLIT || EPI == EPI_F32 || EPI == EPI_DX || EPI == EPI_MASK_SPLIT)) {
+      if (p.K >= kPpMinK || need_pp) {
+        if (!p.plain_loop) hipLaunchKernelGGL((k_gemm_nt_pp<EPI, FP16, true>), dim3(ntiles), dim3(512), 0, s, p);
+        else hipLaunchKernelGGL((k_gemm_nt16<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
         return hipGetLastError();
       }
     }
-#endif
     if (need_pp) return hipErrorInvalidValue;
-#ifndef LIST_X3_SHAPE32      // the hi/lo-split long-K product (fc_0 in bf16x3) on the 16x16x32 shape: 1.52 -> 1.43 ms
+    // the hi/lo-split long-K product (fc_0 in bf16x3) on the 16x16x32 shape: 1.52 -> 1.43 ms
     if constexpr (TERMS == 3 && (EPI == EPI_RELU_SPLIT || EPI == EPI_F32)) {
       if (p.K >= 1024) {
         hipLaunchKernelGGL((k_gemm_nt16<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
         return hipGetLastError();
       }
     }
-#endif
-#ifndef LIST_BWD_SHAPE32     // the backward's data-gradient products (dX, dH) on the 16x16x32 shape: dX 0.87 -> 0.85 ms
+    // the backward's data-gradient products (dX, dH) on the 16x16x32 shape: dX 0.87 -> 0.85 ms
     if constexpr (EPI == EPI_DX || EPI == EPI_MASK_SPLIT) {
       hipLaunchKernelGGL((k_gemm_nt16<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
       return hipGetLastError();
     }
-#endif
     hipLaunchKernelGGL((k_gemm_nt<TERMS, EPI, FP16>), dim3(ntiles), dim3(512), 0, s, p);
   }
   return hipGetLastError();
@@ -1130,7 +1074,7 @@ hipError_t launch_gemm(const GemmParams& p, int terms, int epi, hipStream_t s) {
       if (g.K % 64 || g.K <= 0 || g.m_tiles <= 0 || g.a_rows <= 0 || g.a_rows > g.m_tiles * BM || !g.a || !g.w || !g.out) return hipErrorInvalidValue;
       tiles += g.m_tiles;
     }
-    if (tiles * BM != p.M || p.plain_loop || !kPpShape16) return hipErrorInvalidValue;   // (the 16x16x32 ping-pong kernel only)
+    if (tiles * BM != p.M || p.plain_loop) return hipErrorInvalidValue;   // (the 16x16x32 ping-pong kernel only)
   }
   if (p.M % BM || p.N % BN || p.K % 64 || p.M <= 0) return hipErrorInvalidValue;
   if (p.x3i && p.fmt == FMT_FP16) return hipErrorInvalidValue;

@@ -172,11 +172,7 @@ int64_t chunk_rows_for(size_t bytes, int64_t P, int Kp, int H1, int H2) {
 int fused_fc0_mode() {
   static const int mode = [] {
     const char* e = getenv("LIST_FUSED_FC0");
-#ifdef LIST_FUSED_FC0_DEFAULT_OFF
-    if (!e || !e[0]) return 0;
-#else
     if (!e || !e[0]) return 1;
-#endif
     if (e[0] == '0' && e[1] == 0) return 0;
     if (e[0] == 'x') return 2;
     if (e[0] == '3' && e[1] == 0) return 3;
@@ -213,12 +209,7 @@ bool takes_fused_fc0(const ListQueryArgs* a, const FeatLayout& L) {
 // inference forwards in fp16: fc_1, fc_2 and fc_out as ONE launch (gemm_kernels.hip, k_mlp_tail_f16).  The one
 // predicate behind the dispatch in list_sdf_query_fwd and behind list_query_plan (what a caller's accounting reads).
 bool takes_fused_tail(const ListQueryArgs* a) {
-#ifdef LIST_NO_FUSED_TAIL
-  (void)a;
-  return false;
-#else
   return a->no_activations && a->precision == LIST_PREC_FP16 && a->H2 == 256 && a->H3 == 256 && a->H1 % 64 == 0;
-#endif
 }
 
 }  // namespace
@@ -317,13 +308,9 @@ int list_prep_vox_maps(const ListMap3D maps[LIST_N_VOX_LEVELS], int32_t B, int32
       hipError_t e = launch_split((const float*)m.data, (unsigned short*)dst, nullptr, vol * m.C * B, FMT_FP16,
                                   (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(e, "fp16 conversion launch");
-    } else
-#ifndef LIST_TRANSPOSE_NO_FUSE
-    if (transpose_tile_eligible(m, dst)) {           // launched together below
+    } else if (transpose_tile_eligible(m, dst)) {           // launched together below
       fused_maps[n_fused] = m; fused_out[n_fused] = dst; fused_f16[n_fused] = f16 ? 1 : 0; ++n_fused;
-    } else
-#endif
-    {
+    } else {
       hipError_t e = launch_transpose_vox(m, B, f16, dst, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(e, "transpose_vox launch");
     }
@@ -1016,23 +1003,8 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   mark(LIST_BWD_BEGIN);
   // --- head: scale, dZ3, d fc_out (H3 = relu(fc_2) as the forward left it in its workspace) -------------------
   LIST_TRY(launch_grad_scale(ga->grad_sdf, P, fp16 ? 1 : 0, scale, ga->mlp.b3, colsum, s), "grad_scale launch");
-#ifdef LIST_BWD_REEVAL_FC2
-  // (until round 3, kept for A/B builds: the forward's fused fc_2 + fc_out epilogue wrote no H3, so fc_2 ran again here)
-  GemmParams gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.fmt = fmt;
-  gp.a_hi = fw + ws.h2_hi; gp.a_lo = fw + ws.h2_lo;
-  gp.w_hi = wp + pk.w2_hi; gp.w_lo = wp + pk.w2_lo;
-  gp.bias = (const float*)(wp + pk.b2);
-  gp.M = crow; gp.N = a->H3; gp.K = a->H2;
-  gp.out_hi = plane(bw.h3_hi); gp.out_lo = lo ? plane(bw.h3_lo) : nullptr; gp.ldo = a->H3;
-  LIST_TRY(launch_gemm(gp, terms, EPI_RELU_SPLIT, s), "fc_2 re-evaluation launch");
-  unsigned short* const h3_hi = plane(bw.h3_hi);
-  unsigned short* const h3_lo = lo ? plane(bw.h3_lo) : nullptr;
-#else
   unsigned short* const h3_hi = (unsigned short*)(fw + ws.h3_hi);
   unsigned short* const h3_lo = lo ? (unsigned short*)(fw + ws.h3_lo) : nullptr;
-#endif
   LIST_TRY(launch_head(ga->grad_sdf, order, n_valid, crow, a->H3, h3_hi, (const float*)(wp + pk.w3),
                        scale, plane(bw.dz3_hi), lo ? plane(bw.dz3_lo) : nullptr, fmt, s), "head launch");
   if (ga->mlp.w3)
@@ -1127,7 +1099,6 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   LIST_TRY(hand_over(s, s_direct), "stream fork");
   LIST_TRY(hand_over(s, s_window), "stream fork");
   LIST_TRY(hand_over(s, s_win2), "stream fork");
-  if (!(bwd_knockout() & 1))
   LIST_TRY(wgrad(bw.dz1_hi, bw.dz1_lo, a->H1, fw + ws.x_hi, fw + ws.x_lo, L.Kp, L.Kp, &L, ga->mlp.w0, L.F, s_window),
            "dW0 launch");
   mark(LIST_BWD_WGRAD0);
@@ -1160,28 +1131,23 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   // (bwd_scatter_kernels.hip); the order stays as a second fence and removes the overlap: map gradient, adjoint
   // resize (it needs only the map gradient), then -- behind dW0's event -- the trans_mat gradient.  In line the stages
   // keep their order (and their stage events their meaning).
-  if (!(bwd_knockout() & 32)) {
-    // (LIST_BWD_TRANS_UNORDERED=1, diagnostic: the old order -- the stage right behind the map gradient, beside dW0 --
-    // for tools/trans_noise_probe2.py)
-    static const bool unordered = [] { const char* e = getenv("LIST_BWD_TRANS_UNORDERED"); return e && e[0] == '1'; }();
-    const bool split = forked && ga->grad_trans_mat && !unordered;
-    LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, nslots, bwp + bw.recs, ga->grad_img_map, map_f16,
-                             split ? nullptr : ga->grad_trans_mat, ga->stage_events, s, bwp + bw.img_heavy,
-                             bw.img_heavy_bytes), "image gradient launch");
-    if (ga->grad_img_levels)
-      LIST_TRY(launch_img_grad_to_levels(ga->grad_img_map, a->B, a->map_size, L.img_C, ga->grad_img_levels, s, map_f16,
-                                         scale), "img_grad_to_levels launch");
-    if (split) {
-      // ... on aux_streams[2] where there is one (idle once the 8^3 window level is done) instead of at the end of `s`:
-      // training step 6.43 -> 6.36 ms, 6.52 -> 6.32 with the points on the clamp (LIST_BWD_TRANS_WIN2=0: on `s`)
-      static const bool on_win2 = [] { const char* e = getenv("LIST_BWD_TRANS_WIN2"); return !(e && e[0] == '0'); }();
-      const hipStream_t st = (on_win2 && s_win2 != s) ? s_win2 : s;
-      if (ev_dw0) LIST_TRY(hipStreamWaitEvent(st, ev_dw0, 0), "stream order");
-      LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, nslots, bwp + bw.recs, nullptr, map_f16, ga->grad_trans_mat,
-                               ga->stage_events, st, nullptr, 0), "trans_mat gradient launch");
-    }
+  // (LIST_BWD_TRANS_UNORDERED=1, diagnostic: the old order -- the stage right behind the map gradient, beside dW0 --
+  // for tools/trans_noise_probe2.py)
+  static const bool unordered = [] { const char* e = getenv("LIST_BWD_TRANS_UNORDERED"); return e && e[0] == '1'; }();
+  const bool split = forked && ga->grad_trans_mat && !unordered;
+  LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, nslots, bwp + bw.recs, ga->grad_img_map, map_f16,
+                           split ? nullptr : ga->grad_trans_mat, ga->stage_events, s, bwp + bw.img_heavy,
+                           bw.img_heavy_bytes), "image gradient launch");
+  if (ga->grad_img_levels)
+    LIST_TRY(launch_img_grad_to_levels(ga->grad_img_map, a->B, a->map_size, L.img_C, ga->grad_img_levels, s, map_f16,
+                                       scale), "img_grad_to_levels launch");
+  if (split) {
+    // ... on aux_streams[2] where there is one (idle once the 8^3 window level is done; s_win2 is `s` otherwise)
+    // instead of at the end of `s`: training step 6.43 -> 6.36 ms, 6.52 -> 6.32 with the points on the clamp
+    if (ev_dw0) LIST_TRY(hipStreamWaitEvent(s_win2, ev_dw0, 0), "stream order");
+    LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, nslots, bwp + bw.recs, nullptr, map_f16, ga->grad_trans_mat,
+                             ga->stage_events, s_win2, nullptr, 0), "trans_mat gradient launch");
   }
-  if (bwd_knockout() & 32) { mark(LIST_BWD_IMG); mark(LIST_BWD_TRANS); }
   if (ev_dw0) { (void)hipEventDestroy(ev_dw0); ev_dw0 = nullptr; }
   LIST_TRY(hand_over(s_direct, s), "stream join");
   LIST_TRY(hand_over(s_window, s), "stream join");

@@ -19,12 +19,8 @@ namespace list {
 // them.  The next in-order launch waits for all of them, as for any earlier packet.
 // (Measured: this removes the boundaries, it does not run kernels of one queue side by side -- eight 16-workgroup
 // kernels launched this way still take eight times one; concurrency needs a second stream.)
-// LIST_LAUNCH_IN_ORDER (compile-time definition, or the environment variable of that name set to anything but "0"
-// when the library makes its first query): every launch in order, for A/B runs and as the switch to pull should a
-// runtime mishandle the flag.
-#ifdef LIST_LAUNCH_IN_ORDER
-inline int any_order() { return 0; }
-#else
+// LIST_LAUNCH_IN_ORDER (the environment variable of that name set to anything but "0" when the library makes its
+// first query): every launch in order, for A/B runs and as the switch to pull should a runtime mishandle the flag.
 inline int any_order() {
   static const int flag = [] {
     const char* e = getenv("LIST_LAUNCH_IN_ORDER");
@@ -32,7 +28,6 @@ inline int any_order() {
   }();
   return flag;
 }
-#endif
 #define LIST_LAUNCH(kernel, grid, block, lds, s, order, ...) \
   hipExtLaunchKernelGGL(kernel, grid, block, lds, s, nullptr, nullptr, (order), __VA_ARGS__)
 
@@ -41,17 +36,10 @@ inline int any_order() {
 // fp16 X (round 3): PLAIN stores -- the pieces a gather writes (32 B ... 256 B per sample) merge in L2 into whole lines
 // before they leave; all gathers plain against all non-temporal on one device, four interleaved runs: gather group
 // 0.866 -> 0.841 ms, step 2.110 -> 2.085 ms (no difference in bf16x3, whose pieces are twice as long).
-// -DLIST_X_NT_STORES / -DLIST_X_PLAIN_STORES force one policy for A/B runs.
 template <bool FP16, typename V>
 __device__ __forceinline__ void x_store(const V& v, V* p) {
-#if defined(LIST_X_PLAIN_STORES)
-  *p = v;
-#elif defined(LIST_X_NT_STORES)
-  __builtin_nontemporal_store(v, p);
-#else
   if (FP16) *p = v;
   else __builtin_nontemporal_store(v, p);
-#endif
 }
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -91,9 +79,6 @@ __device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 __device__ __forceinline__ float sat_h(float x) {
-#ifdef LIST_SAT_H_MINMAX          // A/B only: the round-1 clamp (a NaN becomes -65504)
-  return fminf(fmaxf(x, -65504.f), 65504.f);
-#endif
   const float c = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
   return (x != x) ? x : c;
 }
@@ -112,12 +97,7 @@ __device__ __forceinline__ void put_map(void* out, int64_t i, float v, int f16) 
   else ((float*)out)[i] = v;
 }
 __device__ __forceinline__ uint2 half4(const float4& v) {
-#ifdef LIST_HALF4_SCALAR        // A/B: four scalar conversions + shifts instead of two v_cvt_pk_f16_f32
-  return make_uint2((unsigned)f2h(v.x) | ((unsigned)f2h(v.y) << 16),
-                    (unsigned)f2h(v.z) | ((unsigned)f2h(v.w) << 16));
-#else
   return make_uint2(f2h2(v.x, v.y), f2h2(v.z, v.w));
-#endif
 }
 // no clamp: for values known to lie inside the fp16 range (interpolations of fp16 maps: a convex combination
 // of halfs is at most 65504 (1 + 2^-22), which still rounds to 65504); NaN stays NaN
@@ -283,9 +263,6 @@ inline PackedMlpBwd packed_mlp_bwd_layout(int Kp, int H1, int H2, int H3) {
 
 // ---- backward workspace -----------------------------------------------------------------------------------
 constexpr int kSortImagesC = 64, kSortPixCellsC = 8192;      // (= kSortImages, kSortPixCells below; needed above them)
-#ifndef LIST_VOX_GATHER_MIN_DENSITY
-#define LIST_VOX_GATHER_MIN_DENSITY 2.0
-#endif
 constexpr int kColsumRows = 256;         // rows per partial of the bias-gradient column sums
 constexpr int kWgradMaxSplits = 128;
 
@@ -300,7 +277,6 @@ inline size_t img_heavy_bytes(int64_t rows, int Ct) {
 
 struct BwdWorkspace {
   size_t scale;                              // float[4]: s, 1/s, sum(dsdf), -
-  size_t h3_hi, h3_lo;                       // fc_2 activations, re-evaluated (-DLIST_BWD_REEVAL_FC2 builds only)
   size_t dz3_hi, dz3_lo, dz2_hi, dz2_lo, dz1_hi, dz1_lo;
   size_t dx;                                 // [rows][Kp] fp16 (FP16) or fp32
   size_t slab;                               // wgrad partials, fp32
@@ -328,11 +304,6 @@ inline BwdWorkspace bwd_workspace_layout(int64_t rows, int Kp, int H1, int H2, i
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
   w.scale = take(16);
-#ifdef LIST_BWD_REEVAL_FC2      // (A/B builds only: the backward reads H3 where the forward left it, list_capi.hip)
-  w.h3_hi = take((size_t)rows * H3 * 2); w.h3_lo = take((size_t)rows * H3 * 2);
-#else
-  w.h3_hi = w.h3_lo = 0;
-#endif
   w.dz3_hi = take((size_t)rows * H3 * 2); w.dz3_lo = take((size_t)rows * H3 * 2);
   w.dz2_hi = take((size_t)rows * H2 * 2); w.dz2_lo = take((size_t)rows * H2 * 2);
   w.dz1_hi = take((size_t)rows * H1 * 2); w.dz1_lo = take((size_t)rows * H1 * 2);
@@ -543,7 +514,7 @@ struct ScatterParams {
 };
 // buffers of the voxel-side gather (bwd_scatter_kernels.hip); bins == nullptr disables it
 constexpr int64_t kVoxGatherMaxBins = 4194304;      // cells (B * D * H * W) a level may have
-constexpr double kVoxGatherMinDensity = LIST_VOX_GATHER_MIN_DENSITY;   // samples per cell
+constexpr double kVoxGatherMinDensity = 2.0;         // samples per cell
 // mode: ListQueryGradArgs.vox_adjoint; h16 / h16w: scratch for the fp16 image of a direct level / of the two window
 // levels (packed-half atomics), or null
 struct VoxGatherBuffers { int* keys; int* bins; int* sums; void* recs; int mode; void* h16; size_t h16_bytes; void* h16w; size_t h16w_bytes; };
@@ -553,15 +524,8 @@ bool scatter_box_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int c
 // ... and for the formats whose dX is fp32 (bwd_box_split_kernels.hip: bf16 hi + lo operands, fp32 flush)
 bool scatter_box_split_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off);
 hipError_t launch_scatter_vox_box_split(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s);
-bool scatter_f32_diagnostic();      // LIST_SCATTER_F32=1: the window levels flush fp32 atomics (both kernels; tests)
 hipError_t launch_scatter_vox_box(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, _Float16* img16,
                                   hipStream_t s);
-#ifdef LIST_BWD_KNOCKOUT    // diagnostic build (wrong gradients): LIST_BWD_SKIP = bit mask of forked-phase stages left out --
-// 1 dW0, 2 direct-atomic levels, 4 first window level (16^3), 8 second window level (8^3), 16 voxel-side gather, 32 image
-inline int bwd_knockout() { static const int k = [] { const char* e = getenv("LIST_BWD_SKIP"); return e ? atoi(e) : 0; }(); return k; }
-#else
-constexpr int bwd_knockout() { return 0; }
-#endif
 struct ScatterStreams { hipStream_t gather, direct, window, window2; };
 hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
                               const ListVoxLevel grad_vox[LIST_N_VOX_LEVELS], const VoxGatherBuffers& vb,

@@ -8,9 +8,6 @@ namespace list {
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
-#ifdef LIST_GEMM_NO_VMWAIT   // ablation (wrong results): loads are issued but their landing is never waited for
-  if (N != 0) return;
-#endif
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 

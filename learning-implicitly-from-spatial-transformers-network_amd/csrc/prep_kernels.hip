@@ -248,25 +248,14 @@ static bool try_prep_img_nhwc(const ListMap2D& m, int B, int ms, int Ct, int cof
 // slots on arithmetic and index math than the 16-B store it feeds can hide).  No LDS: the 8 lanes of a
 // pixel read 8-channel groups of the same two taps (L1/L2 hits), and write one full 128-B line (fp16:
 // 64 channels; fp32: 256 B) per pixel, 8 pixels per wave-instruction.  Same bits as k_prep_img.
-#ifndef LIST_PREP_RY
-#define LIST_PREP_RY 16
-#endif
-#ifndef LIST_PREP_RY_MAX
-#define LIST_PREP_RY_MAX 32
-#endif
-#ifndef LIST_PREP_PX
-#define LIST_PREP_PX 16
-#endif
-#ifndef LIST_PREP_THREADS
-#define LIST_PREP_THREADS (LIST_PREP_PX * 8)
-#endif
-constexpr int kRowsPx = LIST_PREP_PX;                 // output columns per workgroup (x 8 channel octets = 128 threads)
+constexpr int kRowsPx = 16;                 // output columns per workgroup (x 8 channel octets = 128 threads)
 constexpr int kRowsCg = 64;                 // channels per workgroup
+constexpr int kRowsRyMax = 32;              // output rows per workgroup, at most
 struct PrepRowsLevel { ListMap2D m; int coff, wg_begin, cgroups, vec, RY, nyt; };
 struct PrepRowsArgs { PrepRowsLevel lv[LIST_N_IMG_LEVELS]; int n_levels, B, ms, Ct, nxt; };
 
 template <int F16>
-__global__ __launch_bounds__(LIST_PREP_THREADS) void k_prep_img_rows(PrepRowsArgs a, void* __restrict__ out) {
+__global__ __launch_bounds__(kRowsPx * 8) void k_prep_img_rows(PrepRowsArgs a, void* __restrict__ out) {
   // level-major block order: consecutive workgroups are x tiles of one (level, channel group, row block), 32 KB
   // apart in the output.  (Pixel-tile-major -- the 16 channel groups of a pixel tile side by side, so that a
   // pixel's 2 KB leave together -- measured 0.73 ms instead of 0.19: the writes of a moment then fall on few
@@ -274,11 +263,7 @@ __global__ __launch_bounds__(LIST_PREP_THREADS) void k_prep_img_rows(PrepRowsArg
   // XCD-contiguous: workgroups are dealt round-robin over the 8 XCDs, so consecutive block ids -- neighbouring x
   // tiles, which read the same source lines -- would sit behind 8 different L2s and each fetch them again (PMC:
   // 0.64 GB fetched for 0.15 GB of source).  Every XCD gets one contiguous eighth of the logical order instead.
-#ifdef LIST_PREP_NO_XCD
-  const int bid = blockIdx.x;
-#else
   const int bid = xcd_contiguous_block(blockIdx.x, gridDim.x);
-#endif
   int l = 0;
 #pragma unroll
   for (int i = 1; i < LIST_N_IMG_LEVELS; ++i)
@@ -307,12 +292,8 @@ __global__ __launch_bounds__(LIST_PREP_THREADS) void k_prep_img_rows(PrepRowsArg
   const float wx1 = fx - (float)x0, wx0 = 1.f - wx1;
   const float* p0 = m.data + (int64_t)b * m.sb + (int64_t)c * m.sc + (int64_t)x0 * m.sw;
   const float* p1 = m.data + (int64_t)b * m.sb + (int64_t)c * m.sc + (int64_t)x1 * m.sw;
-#ifndef LIST_PREP_NO_PAIR
   // NCHW-like source (x contiguous): taps x0, x1 = x0 + 1 (or x0 at the right edge) come from the pair (xb, xb + 1)
   const bool pair = !vec && m.sw == 1 && m.W >= 2;
-#else
-  const bool pair = false;
-#endif
   const int xb = min(x0, m.W - 2);
   const bool sel0 = x0 != xb, sel1 = x1 != xb;
   const float* pb = m.data + (int64_t)b * m.sb + (int64_t)c * m.sc + (int64_t)xb;
@@ -381,7 +362,6 @@ __global__ __launch_bounds__(LIST_PREP_THREADS) void k_prep_img_rows(PrepRowsArg
     for (int k = 0; k < 8; ++k) o[k] = top[k] * wy0 + bot[k] * wy1;
     if (!active) continue;
     if (F16) {
-#ifndef LIST_PREP_SAT_ALWAYS
       // saturate only the rows that need it: one compare per value (|x| is a free source modifier; a NaN compares
       // false and converts to NaN, +-inf compares true) instead of the 3-instruction NaN-preserving clamp per value
       // -- the kernel is bound by vector issue and the clamp was a third of its steady-state row
@@ -394,17 +374,10 @@ __global__ __launch_bounds__(LIST_PREP_THREADS) void k_prep_img_rows(PrepRowsArg
       }
       const uint2 lo = half4_inrange(make_float4(o[0], o[1], o[2], o[3]));
       const uint2 hi = half4_inrange(make_float4(o[4], o[5], o[6], o[7]));
-#else
-      const uint2 lo = half4(make_float4(o[0], o[1], o[2], o[3]));
-      const uint2 hi = half4(make_float4(o[4], o[5], o[6], o[7]));
-#endif
-#ifndef LIST_PREP_NO_NT          // streamed once, read again only by the 2-D gather: keep it out of the L2 working set
+      // streamed once, read again only by the 2-D gather: keep it out of the L2 working set
       __builtin_nontemporal_store((f32x4){__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y),
                                           __builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y)},
                                   (f32x4*)((unsigned short*)out + oi));
-#else
-      *(uint4*)((unsigned short*)out + oi) = make_uint4(lo.x, lo.y, hi.x, hi.y);
-#endif
     } else {
       *(float4*)((float*)out + oi) = make_float4(o[0], o[1], o[2], o[3]);
       *(float4*)((float*)out + oi + 4) = make_float4(o[4], o[5], o[6], o[7]);
@@ -420,7 +393,6 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
                            int f16, void* out, hipStream_t s, int n_levels) {
   int coff = 0;
   if (n_levels <= 0) return hipSuccess;
-#ifndef LIST_PREP_IMG_NO_ROWS
   {
     PrepRowsArgs a;
     a.n_levels = 0; a.B = B; a.ms = map_size; a.Ct = Ct;
@@ -438,11 +410,8 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
       // (down-sampling: 2 per row), many where ten output rows share one (the 14 px level)
       {
         const float sy = (float)(m.H - 1) / (float)(map_size - 1);
-        int ry = (int)(3.3f / (sy > 0.05f ? sy : 0.05f) + 0.5f);
-#ifdef LIST_PREP_RY_UNIFORM
-        ry = LIST_PREP_RY;
-#endif
-        lv.RY = ry < 2 ? 2 : (ry > LIST_PREP_RY_MAX ? LIST_PREP_RY_MAX : ry);
+        const int ry = (int)(3.3f / (sy > 0.05f ? sy : 0.05f) + 0.5f);
+        lv.RY = ry < 2 ? 2 : (ry > kRowsRyMax ? kRowsRyMax : ry);
         lv.nyt = (map_size + lv.RY - 1) / lv.RY;
       }
       lv.vec = (m.sc == 1 && (m.sw % 4) == 0 && (m.sh % 4) == 0 && (m.sb % 4) == 0 &&
@@ -451,16 +420,6 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
       co += m.C;
     }
     if (all && wgs > 0 && wgs < 2147483647LL) {
-#ifdef LIST_PREP_PER_LEVEL           // profiling only: one launch per level, so that a kernel trace shows each
-      for (int i = 0; i < a.n_levels; ++i) {
-        PrepRowsArgs one = a;
-        one.n_levels = 1; one.lv[0] = a.lv[i]; one.lv[0].wg_begin = 0;
-        const unsigned n = (unsigned)((int64_t)B * a.lv[i].nyt * a.lv[i].cgroups * a.nxt);
-        if (f16) hipLaunchKernelGGL(k_prep_img_rows<1>, dim3(n), dim3(kRowsPx * 8), 0, s, one, out);
-        else hipLaunchKernelGGL(k_prep_img_rows<0>, dim3(n), dim3(kRowsPx * 8), 0, s, one, out);
-      }
-      return hipGetLastError();
-#endif
       if (f16)
         hipLaunchKernelGGL(k_prep_img_rows<1>, dim3((unsigned)wgs), dim3(kRowsPx * 8), 0, s, a, out);
       else
@@ -468,7 +427,6 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
       return hipGetLastError();
     }
   }
-#endif
   for (int i = 0; i < n_levels; ++i) {
     const ListMap2D& m = maps[i];
     hipError_t fe = hipSuccess;
@@ -567,7 +525,7 @@ struct ProjSumArgs { ListMap2D src[kProjMaxSrc]; int n_src, B, ms, Ct, coff, H1,
 
 // NL = number of source levels (compile time: the per-level row pairs live in registers, 16 per level)
 template <int F16, int NL, int SRC16>
-__global__ __launch_bounds__(LIST_PREP_THREADS) void k_proj_resize_sum(ProjSumArgs a, void* __restrict__ out) {
+__global__ __launch_bounds__(kRowsPx * 8) void k_proj_resize_sum(ProjSumArgs a, void* __restrict__ out) {
   const int bid = xcd_contiguous_block(blockIdx.x, gridDim.x);
   const int cgroups = a.H1 / kRowsCg;
   int idx = bid;
@@ -689,7 +647,7 @@ hipError_t launch_proj_resize_sum(const ListMap2D* src, int n_src, int B, int ma
   // (measured at the metric's three levels, sy_max 0.40: 4 / 8 / 16 / 24 / 32 rows -> the whole prep 0.191 / 0.179 / 0.171 /
   // 0.169 / 0.175 ms: the first row of a workgroup fetches two source rows of EVERY level, so twice k_prep_img_rows's rows)
   int ry = (int)(6.6f / (sy_max > 0.05f ? sy_max : 0.05f) + 0.5f);
-  a.RY = ry < 2 ? 2 : (ry > LIST_PREP_RY_MAX ? LIST_PREP_RY_MAX : ry);
+  a.RY = ry < 2 ? 2 : (ry > kRowsRyMax ? kRowsRyMax : ry);
   a.nyt = (map_size + a.RY - 1) / a.RY;
   a.nxt = (map_size + kRowsPx - 1) / kRowsPx;
   const int64_t wgs = (int64_t)B * a.nyt * (a.H1 / kRowsCg) * a.nxt;
@@ -743,13 +701,10 @@ __global__ __launch_bounds__(256) void k_transpose_vox(ListMap3D m, int c_begin,
   }
 }
 
-#ifndef LIST_TR_TILE
-#define LIST_TR_TILE 2048
-#endif
 // elements per tile.  Measured (all five levels, 2.15 GB): 16384: 0.464 ms, 8192: 0.428, 4096: 0.405, 2048: 0.353
 // (6.1 TB/s, the rate of a plain copy), 1024: 0.369 -- 8-KB tiles keep 4x as many workgroups, i.e. independent
 // load -> LDS -> store chains, in flight per CU as the 32-KB tiles of round 1
-constexpr int kTrTile = LIST_TR_TILE;
+constexpr int kTrTile = 2048;
 // Fast path (spatially contiguous source, C in {16,32,64,128}): a workgroup moves a kTrTile-element
 // tile = V voxels x C channels (V = kTrTile / C).  16-B global loads along the voxel axis, 16-B global
 // stores along the channel axis (fully contiguous), LDS image [v][c] with the element index XORed by

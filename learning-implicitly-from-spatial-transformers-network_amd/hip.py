@@ -727,9 +727,7 @@ def sdf_query_backward(ctx, grad_sdf, packed_bwd, want_mlp=True, want_img=True, 
         ga.stage_events = C.cast(stage_events, C.POINTER(C.c_void_p))
     if overlap:        # dW0 | atomic scatters | window scatters | gathers run side by side (joined before return)
         with _AuxStreams(dev) as (a0, a1, a2), torch.cuda.device(dev):
-            ga.aux_streams[0], ga.aux_streams[1] = a0.cuda_stream, a1.cuda_stream
-            if os.environ.get("LIST_BWD_WIN2_OWN", "1") != "0":
-                ga.aux_streams[2] = a2.cuda_stream
+            ga.aux_streams[0], ga.aux_streams[1], ga.aux_streams[2] = a0.cuda_stream, a1.cuda_stream, a2.cuda_stream
             # The library joins the side streams back into the caller's stream before it returns -- on success AND
             # on every error path -- so whatever runs on the caller's stream afterwards (including the caching
             # allocator handing these buffers to a later allocation on that stream) is ordered behind the side
