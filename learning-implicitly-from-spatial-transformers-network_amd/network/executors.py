@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import evaluate, mesh, parallel, utils
+from .. import chamfer, evaluate, mesh, parallel, utils
 from . import losses as L
 
 
@@ -27,7 +27,10 @@ class CoarseNet:
         self.coarse_points = config.coarse_point_density
 
     def calc_loss(self, pred, gt):
-        return self.loss_fn(pred, gt)[0] * 1000
+        # on the GPU the HIP loss (include/list_loss.h: no B x N x M matrix, a deterministic backward); CPU tensors
+        # keep the torch path
+        loss_fn = chamfer.chamfer_distance if pred.is_cuda else self.loss_fn
+        return loss_fn(pred, gt)[0] * 1000
 
     def _device(self):
         return next(self.model.parameters()).device
