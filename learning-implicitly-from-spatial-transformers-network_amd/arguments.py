@@ -23,6 +23,12 @@ def build_parser():
     p.add_argument("--mcube_znum", type=int, default=128,
                    help="resolution of the inference query grid (decoupled from --vox_res)")
     p.add_argument("--test_pointnum", type=int, default=65536)
+    p.add_argument("--refine_stride", type=int, default=0, choices=[0, 2, 4, 8],
+                   help="coarse-to-fine query grid (refine.py): query the stride-s lattice and the fine points of the "
+                        "bricks near the surface, interpolate the rest; 0 = the dense grid")
+    p.add_argument("--refine_band", type=float, default=None,
+                   help="with --refine_stride: a brick whose corners come within this distance of the iso-level is "
+                        "refined (default: the brick's diagonal)")
     p.add_argument("--save_volume", action="store_true",
                    help="test.py: also write each item's raw SDF volume (<stem>_sdf.npy) next to its mesh")
     p.add_argument("--chunk_s", type=int, default=0)

@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import chamfer, evaluate, mesh, parallel, utils
+from .. import chamfer, evaluate, mesh, parallel, refine as RF, utils
 from . import losses as L
 
 
@@ -68,6 +68,10 @@ class LIST:
         self.query_res = getattr(config, "mcube_znum", None) or config.vox_res
         self.bb_min, self.bb_max, self.vox_res = config.bb_min, config.bb_max, config.vox_res
         self.loss_sdf = L.SDFLoss(self.sdf_scale)
+        # coarse-to-fine grid for test(): --refine_stride 0 is the dense grid
+        self.refine_stride = getattr(config, "refine_stride", 0) or None
+        self.refine_band = getattr(config, "refine_band", None)
+        self.last_grid_stats = None
 
     def _device(self):
         return self.device or next(self.model.parameters()).device
@@ -105,13 +109,20 @@ class LIST:
         return pred, (self.calc_loss(pred, [occ_gt, sdf_gt]) if calc_loss else [])
 
     @torch.no_grad()
-    def predict_grid(self, img, transmat=None, res=None, shard=True):
+    def predict_grid(self, img, transmat=None, res=None, shard=True, refine=None, band=None, level=0.0):
         """SDF on the regular res^3 grid over [-0.5,0.5]^3 (reference executors.py:191-231) ->
         float32 tensor [res,res,res] on the device, already divided by sdf_scale.
 
         The grid is generated on the device chunk by chunk (no host->device point copies, no
         per-chunk .cpu()); with torch.distributed initialised and shard=True the query axis is split
-        over the ranks and all-gathered."""
+        over the ranks and all-gathered.
+
+        refine=s (2, 4 or 8): the coarse-to-fine grid of refine.predict_grid_refined -- the network is queried on the
+        stride-s lattice and at the fine points of the bricks near the iso-level `level` (band: refine.default_band
+        when None); the other points are interpolated.  Queried points equal the dense grid's bit for bit; the
+        counts land in self.last_grid_stats.  refine=None: every point is queried."""
+        if refine:
+            return self._predict_grid_refined(img, transmat, res, shard, refine, band, level)
         net = _unwrap(self.model)
         dev = img.device
         res = res or self.query_res
@@ -141,10 +152,32 @@ class LIST:
             out = parallel.gather_ragged_points(out, total)
         return (out / self.sdf_scale).view(res, res, res), occ, vox_feat
 
+    def _predict_grid_refined(self, img, transmat, res, shard, stride, band, level):
+        net = _unwrap(self.model)
+        dev = img.device
+        res = res or self.query_res
+        feat_l2, vox_feat, transmat, _, occ = net.encode(img, transmat)
+        rank, world = parallel.world_info() if shard else (0, 1)
+        if world > 1:        # as the dense grid: every rank samples rank 0's maps
+            parallel.broadcast_from_rank0(list(feat_l2) + list(vox_feat) + [transmat, occ])
+        ms = net.percep_pooling.map_size
+        project = res ** 3 >= 4 * ms * ms             # the dense grid's decision: every queried point gets its bits
+
+        def query(pts):
+            # the dense grid's per-point arithmetic, the division by sdf_scale included (the same torch expression)
+            return net.query_sdf(pts, feat_l2, vox_feat, transmat, ordered_points=True,
+                                 project_percep=project)[0] / self.sdf_scale
+
+        vol, self.last_grid_stats = RF.predict_grid_refined(query, res, int(stride), band=band, level=level,
+                                                            device=dev, step=max(int(self.test_pointnum), 1 << 20),
+                                                            shard=shard)
+        return vol, occ, vox_feat
+
     def test(self, batch, eval_pred=False):
         img = batch["rgb_image"].to(self._device())
         transmat = batch["transmat"].to(self._device()) if "transmat" in batch else None
-        volume, occ, vox_feat = self.predict_grid(img, transmat)
+        volume, occ, vox_feat = (self.predict_grid(img, transmat, refine=self.refine_stride, band=self.refine_band)
+                                 if self.refine_stride else self.predict_grid(img, transmat))
         # marching cubes on the device, where the volume lies (mesh.marching_cubes: mcubes' surface of -volume at 0)
         pred_mesh = mesh.Mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5))
         score = self.eval(pred_mesh, batch.get("gt_mesh")) if eval_pred else {}

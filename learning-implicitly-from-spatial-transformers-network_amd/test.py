@@ -7,8 +7,10 @@ query grid with the HIP path and extract the iso-surface on the GPU (mesh.marchi
         --mcube_znum 256
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py ...    # query axis sharded over GPUs
 
-`--save_volume` also writes the raw [res,res,res] SDF volume (<stem>_sdf.npy).  `--eval_pred` scores every item whose
-dataset gives a ground-truth mesh (evaluate.eval_mesh on the device: Chamfer-L2, precision / recall / F-score, IoU) and
+`--refine_stride s` (2, 4, 8) queries the coarse-to-fine grid of refine.py instead of every grid point: the stride-s
+lattice and the fine points near the surface, the rest interpolated (`--refine_band` sets how near).  `--save_volume`
+also writes the [res,res,res] SDF volume (<stem>_sdf.npy; with --refine_stride the filled one).  `--eval_pred` scores
+every item whose dataset gives a ground-truth mesh (evaluate.eval_mesh on the device: Chamfer-L2, precision / recall / F-score, IoU) and
 writes <results_dir>test_objs/<cat>.csv, one row per item and a final `Mean` row, as the reference does; items without
 one (the synthetic datasets) are reported as skipped."""
 import csv
@@ -72,12 +74,23 @@ def test_all(config, save_volume=None, eval_pred=None):
     for it in items:
         batch = dataset.get_testdata(it["cat_id"], it["shape_id"], it["cam_id"])
         t0 = time.time()
-        volume, _, _ = executor.predict_grid(batch["rgb_image"].to(config.device), batch.get("transmat"))
+        stride = getattr(config, "refine_stride", 0)
+        if stride:
+            volume, _, _ = executor.predict_grid(batch["rgb_image"].to(config.device), batch.get("transmat"),
+                                                 refine=stride, band=getattr(config, "refine_band", None))
+        else:
+            volume, _, _ = executor.predict_grid(batch["rgb_image"].to(config.device), batch.get("transmat"))
         torch.cuda.synchronize()
         dt = time.time() - t0
         if rank0:
-            print(f"{it['cat_id']}/{it['shape_id']}: {volume.numel()} queries in {dt:.3f} s "
-                  f"({volume.numel() / dt / 1e6:.2f} M points/s incl. encoders)")
+            if stride:
+                st = executor.last_grid_stats
+                print(f"{it['cat_id']}/{it['shape_id']}: {st['queried']} queries = {100.0 * st['fraction']:.2f} % of "
+                      f"the {volume.numel()} grid points (stride {stride}) in {dt:.3f} s "
+                      f"({volume.numel() / dt / 1e6:.2f} M grid points/s incl. encoders)")
+            else:
+                print(f"{it['cat_id']}/{it['shape_id']}: {volume.numel()} queries in {dt:.3f} s "
+                      f"({volume.numel() / dt / 1e6:.2f} M points/s incl. encoders)")
             stem = utils.ensure_dir(out_dir + it["cat_id"] + "/") + f"{it['shape_id']}_{it['cam_id']}"
             if save_volume:
                 np.save(stem + "_sdf.npy", volume.cpu().numpy())

@@ -73,15 +73,16 @@ def grid_points_on_device(minimum, maximum, res, device, begin=0, end=None):
     total = res ** 3
     end = total if end is None else end
     idx = torch.arange(begin, end, device=device, dtype=torch.int64)
-    step = (maximum - minimum) / (res - 1) if res > 1 else 0.0
     i, j, k = idx // (res * res), (idx // res) % res, idx % res
+    return torch.stack([grid_axis_coord(t, minimum, maximum, res) for t in (i, j, k)], dim=1)
 
-    def coord(t):
-        v = minimum + t.to(torch.float64) * step
-        v = torch.where(t == res - 1, torch.full_like(v, float(maximum)), v)   # linspace pins the end
-        return v.to(torch.float32)
 
-    return torch.stack((coord(i), coord(j), coord(k)), dim=1)
+def grid_axis_coord(t, minimum, maximum, res):
+    """float32 coordinate of the int64 axis indices t on grid_points_on_device's grid (float64 arithmetic, end pinned)."""
+    step = (maximum - minimum) / (res - 1) if res > 1 else 0.0
+    v = minimum + t.to(torch.float64) * step
+    v = torch.where(t == res - 1, torch.full_like(v, float(maximum)), v)   # linspace pins the end
+    return v.to(torch.float32)
 
 
 def get_kdtree(bb_min, bb_max, res):
