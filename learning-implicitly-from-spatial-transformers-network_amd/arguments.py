@@ -89,6 +89,10 @@ def build_parser():
                    help="fp16: the 3-D encoder runs under autocast (MIOpen half kernels, 2.5x faster at 128^3) and "
                         "hands fp16 channels-last levels to the query path, which uses them where they lie; "
                         "changes the features by ~3e-4, so it is opt-in and meant for --precision fp16")
+    p.add_argument("--vox_encoder", default="torch", choices=["torch", "hip"],
+                   help="hip: the 3-D encoder's inference forward runs in HIP (voxenc.py: fp16 operands on the matrix "
+                        "cores, fp16 channels-last levels used in place by the query path); eval mode and no gradients "
+                        "only, meant for --precision fp16.  Training keeps 'torch'")
     p.add_argument("--channels_last", type=_bool, default=True,
                    help="run the encoders that feed the query path in channels-last memory format")
     p.add_argument("--synthetic_len", type=int, default=64, help="items per epoch of the synthetic datasets")

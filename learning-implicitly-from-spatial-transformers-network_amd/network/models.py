@@ -33,6 +33,11 @@ class LIST(nn.Module):
         # list_prep_vox_maps is a no-op (MIOpen NDHWC/NHWC convolutions: same results, same speed).
         self.channels_last = bool(getattr(config, "channels_last", True))
         self.vox_encoder_half = getattr(config, "vox_encoder_precision", "fp32") == "fp16"
+        # "hip": the eval-mode forward of the 3-D encoder runs in HIP (voxenc.py) for tensors on a HIP device; the
+        # training forward and the backward are the torch module's (a forward in train() raises, it never falls back)
+        self.vox_encoder_kind = getattr(config, "vox_encoder", "torch")
+        if self.vox_encoder_kind not in ("torch", "hip"):
+            raise ValueError(f"vox_encoder = {self.vox_encoder_kind!r}: 'torch' or 'hip'")
         self.vox_encoder = M.VoxelEncoder2(config.im_enc_layers)
         self.sdf_decoder = M.VoxelDecoder2(enc_feat_size, 256)
         self.sdf_decoder.precision = getattr(config, "precision", "bf16x3")
@@ -67,6 +72,9 @@ class LIST(nn.Module):
             code = torch.cat([coarse, feat_g2.reshape(img.shape[0], -1)], dim=1)
             trans_mat = self.spatial_transformer(code).reshape(-1, 4, 3)
         occ = self.create_occ(pc)
+        if self.vox_encoder_kind == "hip" and occ.is_cuda:
+            from .. import voxenc
+            return feat_l2, voxenc.forward(self.vox_encoder, occ), trans_mat, pc, occ   # fp16 channels-last levels
         if self.vox_encoder_half and occ.is_cuda:
             with torch.autocast("cuda", dtype=torch.float16):
                 vox_feat = self.vox_encoder(occ)

@@ -54,6 +54,11 @@ with torch.no_grad():
         err = max(float((a.float() - b).abs().max()) for a, b in zip(v16, vox))
         print(f"vox_encoder autocast {name}     {t:8.3f} ms   max|diff| vs fp32 {err:.3e}  formats "
               f"{[('cl' if a.is_contiguous(memory_format=torch.channels_last_3d) else 'nc') for a in v16]}")
+    from list_amd import voxenc                                                # --vox_encoder hip
+    pk = voxenc.pack(net.vox_encoder)
+    t, vh = timed(lambda: voxenc.encode(occ, pk))
+    err = max(float((a.float() - b).abs().max()) for a, b in zip(vh, vox))
+    print(f"vox_encoder HIP (fp16 MFMA)   {t:8.3f} ms   max|diff| vs fp32 {err:.3e}")
     net2 = utils.get_class("network.models.LIST")(cfg).to(dev).eval()          # plain NCDHW encoder
     net2.vox_encoder.load_state_dict(net.vox_encoder.state_dict())
     t, _ = timed(lambda: net2.vox_encoder(occ))
