@@ -251,6 +251,37 @@ def pooled_view(ws, B, R, layers, stage):
     return ws[o:o + 2 * n].view(torch.float16).view(B, D, D, D, Cc).permute(0, 4, 1, 2, 3)
 
 
+def mid_view(ws, B, R, layers, stage):
+    """The activation between the two convolutions of `stage` (3 .. 7) in a workspace: float16 [B,C,D,D,D] view with
+    channels_last_3d strides, C = layers[stage + 1], D = R >> (stage - 3).  One buffer serves every stage: the view
+    holds that stage's activation only between its two launches (see encode_steps)."""
+    import torch
+    o = 2 * _align(B * R ** 3 * 4)
+    D, Cc = R >> (stage - 3), layers[stage + 1]
+    n = B * D ** 3 * Cc
+    return ws[o:o + 2 * n].view(torch.float16).view(B, D, D, D, Cc).permute(0, 4, 1, 2, 3)
+
+
+def encode_steps(occ, packed, begin, end, buffers=None):
+    """Launches [begin, end) of the forward, in step_names() order, on `buffers` (those a previous call returned; None
+    allocates them).  Returns (levels, ws, buffers): the six level views of encode(), the workspace and the handle to
+    pass on.  The launches before `begin` must have run on the same buffers."""
+    import torch
+    if buffers is None:
+        buffers = _buffers(occ, packed)
+    B, R, ws, store = buffers
+    if tuple(occ.shape) != (B, R, R, R):
+        raise RuntimeError(f"voxenc.encode_steps: occ of shape {tuple(occ.shape)} on buffers of B = {B}, R = {R}")
+    occ = occ.contiguous()
+    arr, n = _layers_arg(packed.layers)
+    outs = (C.c_void_p * N_LEVELS)(*[s.data_ptr() for s in store])
+    with torch.cuda.device(occ.device):
+        _check(load().list_voxenc_forward_steps(occ.data_ptr(), B, R, arr, n, packed.blob.data_ptr(),
+                                                packed.blob.numel(), ws.data_ptr(), ws.numel(), outs, int(begin),
+                                                int(end), hip._stream()), "list_voxenc_forward_steps")
+    return _views(store), ws, buffers
+
+
 def step_names(layers):
     names = ["conv_0", "conv_1", "conv_2"]
     for l in range(3, N_STAGES):
@@ -307,15 +338,16 @@ def forward(module, occ):
 
 # ---- host restatement ------------------------------------------------------------------------------------------------
 def _conv3(x, w):
-    """x float64 [B,D,D,D,Cin], w float64 [Cout,Cin,3,3,3] -> float64 [B,D,D,D,Cout]: 3x3x3 cross-correlation, zero
-    padding 1, accumulated in float64."""
-    B, D = x.shape[0], x.shape[1]
+    """x float64 [B,Dz,Dy,Dx,Cin], w float64 [Cout,Cin,3,3,3] -> float64 [B,Dz,Dy,Dx,Cout]: 3x3x3 cross-correlation,
+    zero padding 1, accumulated in float64."""
+    Dz, Dy, Dx = x.shape[1:4]
     xp = np.pad(x, ((0, 0), (1, 1), (1, 1), (1, 1), (0, 0)))
+    wt = np.ascontiguousarray(w.transpose(2, 3, 4, 1, 0))    # [3,3,3,Cin,Cout]: contiguous taps, or the GEMM crawls
     out = np.zeros(x.shape[:4] + (w.shape[0],), dtype=np.float64)
     for kz in range(3):
         for ky in range(3):
             for kx in range(3):
-                out += xp[:, kz:kz + D, ky:ky + D, kx:kx + D, :] @ w[:, :, kz, ky, kx].T
+                out += xp[:, kz:kz + Dz, ky:ky + Dy, kx:kx + Dx, :] @ wt[kz, ky, kx]
     return out
 
 

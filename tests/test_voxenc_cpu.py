@@ -8,9 +8,15 @@ import numpy as np
 import pytest
 import torch
 
+import copy
+import sys
+
 from oracle import fill, synth
 from list_amd import arguments, hip, utils, voxenc
 from list_amd.network.modules import VoxelEncoder2
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _voxenc_check as vc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAYERS = [1, 1, 1, 1, 16, 32, 64, 128, 128]
@@ -56,6 +62,36 @@ def test_exact_restatement_is_the_torch_module(kind):
         err, top = float(np.abs(a - b).max()), float(np.abs(b).max())
         print(f"level {k}: max|restatement - torch fp64| = {err:.3e}, max|level| = {top:.3e}")
         assert top > 0 and err <= 1e-10 * top, (k, err, top)
+
+
+@pytest.mark.parametrize("layers,R", [(LAYERS, 48), (vc.LIST_A, 48), (vc.LIST_B, 32)])
+def test_exact_restatement_is_the_torch_module_at_other_shapes(layers, R):
+    """The same bound at a grid whose levels end in partial bricks (48, 24, 12, 6, 3) and at the two layer lists the
+    GPU tests add (a 64- and a 128-channel level 1, narrowing and widening stages)."""
+    m = fill.fill_state(VoxelEncoder2(layers), seed=2).double().eval()
+    occ = random_occ(5, 1, R)
+    with torch.no_grad():
+        ref = m(torch.from_numpy(occ).double())
+    got = voxenc.encode_cpu(occ, voxenc.params_of(m), storage="exact")
+    for k, (a, b) in enumerate(zip(got, ref)):
+        b = b.numpy()
+        assert a.shape == b.shape and a.shape[1:] == (layers[k + 3],) + (R >> max(k - 1, 0),) * 3
+        err, top = float(np.abs(a - b).max()), float(np.abs(b).max())
+        print(f"layers {layers} R={R} level {k}: max|restatement - torch fp64| = {err:.3e}, max|level| = {top:.3e}")
+        assert top > 0 and err <= 1e-10 * top, (k, err, top)
+
+
+def test_torch_module_raises_at_r16_where_the_hip_path_does_not():
+    """An asymmetry, written down: VoxelEncoder2.forward max-pools after its LAST stage too (the result is thrown
+    away), and at R = 16 that stage's volume is 1^3, so the torch module raises.  The HIP path does not pool there
+    and accepts R = 16 (include/list_voxenc.h: 16 <= R; the query path's tiny case gathers from a 16^3 pyramid); its
+    reference at R = 16 is the restatement, which is the torch module at every size both accept (tests above)."""
+    m = fill.fill_state(VoxelEncoder2(LAYERS), seed=2).eval()
+    with torch.no_grad(), pytest.raises(RuntimeError):
+        m(torch.zeros(1, 16, 16, 16))
+    assert voxenc.workspace_bytes(1, 16, LAYERS) == voxenc.workspace_bytes_closed_form(1, 16, LAYERS) > 0
+    levels = voxenc.encode_cpu(random_occ(5, 1, 16), voxenc.params_of(m), storage="fp16")
+    assert [v.shape[2] for v in levels] == [16, 16, 8, 4, 2, 1] and all(np.isfinite(v).all() for v in levels)
 
 
 def test_fp16_restatement_level0_is_the_reference_golden(golden_dir):
@@ -114,6 +150,21 @@ def test_buffer_sizes_match_their_closed_forms():
             == voxenc.workspace_bytes_closed_form(B, R, LAYERS)
     # B = 1, R = 128: two fp32 volumes (8 MiB each), the 16-channel fp16 activation (64 MiB), four pooled levels
     assert voxenc.workspace_bytes(1, 128, LAYERS) == 2 * 8388608 + 67108864 + 8388608 + 2097152 + 524288 + 131072
+
+
+@pytest.mark.parametrize("layers", [vc.LIST_A, vc.LIST_B, [1, 1, 1, 1, 16, 16, 16, 16, 16],
+                                    [1, 1, 1, 1, 128, 128, 128, 128, 128]])
+def test_buffer_sizes_match_their_closed_forms_at_other_shapes(layers):
+    assert voxenc.weight_bytes(layers) == _closed_weight_bytes(layers) == voxenc.weight_bytes_closed_form(layers)
+    for B in (1, 3):
+        for R in (16, 48, 80, 96, 256):
+            assert voxenc.workspace_bytes(B, R, layers) == _closed_workspace_bytes(B, R, layers) \
+                == voxenc.workspace_bytes_closed_form(B, R, layers)
+    for R in (16, 48, 80, 96, 256):
+        assert voxenc.workspace_bytes(3, R, LAYERS) == _closed_workspace_bytes(3, R, LAYERS)
+    # B = 1, R = 256, default layers: two fp32 volumes (64 MiB each), the 16-channel activation (512 MiB), four pooled
+    assert voxenc.workspace_bytes(1, 256, LAYERS) == 2 * (64 << 20) + (512 << 20) + (64 << 20) + (16 << 20) \
+        + (4 << 20) + (1 << 20)
 
 
 def test_refusals_carry_a_message_without_a_gpu():
@@ -182,3 +233,132 @@ def test_forward_refuses_training_mode_and_gradients():
         voxenc.forward(m, occ)
     with torch.no_grad(), pytest.raises(RuntimeError, match="HIP device"):
         voxenc.forward(m, occ)                              # a CPU module: an error, never the torch module
+
+
+# ---- the per-launch check (tests/_voxenc_check.py) has teeth ---------------------------------------------------------
+def _bf16(w):
+    return torch.from_numpy(w.astype(np.float32)).bfloat16().double().numpy()
+
+
+def _fault_tap(x, L, y):
+    """One tap (dz, dy, dx) = (1, 0, 2) dropped for all channels."""
+    M = copy.copy(L)
+    M.w = L.w.copy()
+    M.w[:, :, 1, 0, 2] = 0
+    return vc.emulate(x, M)
+
+
+def _fault_brick_halo(x, L, y):
+    """The brick at the origin reads zeros for the halo beyond one of its faces (+x if the volume has a second brick
+    there, else +y)."""
+    bad = np.array(x, dtype=np.float64)
+    if x.shape[3] > 8:
+        bad[:, :, :, 8] = 0
+    else:
+        bad[:, :, 4] = 0
+    out = y.copy()
+    out[:, 0:4, 0:4, 0:8] = vc.emulate(bad, L)[:, 0:4, 0:4, 0:8]
+    return out
+
+
+def _fault_face_neighbour(x, L, y):
+    """At the volume's x = 0 face the halo holds the neighbouring voxel instead of zero."""
+    xe = np.concatenate([np.asarray(x)[:, :, :, 0:1], np.asarray(x)], axis=3)
+    out = y.copy()
+    out[:, :, :, 0] = vc.emulate(xe, L)[:, :, :, 1]
+    return out
+
+
+def _fault_tiles(x, L, y):
+    """Output channels 0 .. 15 and 16 .. 31 swapped."""
+    out = y.copy()
+    out[..., 0:16], out[..., 16:32] = y[..., 16:32], y[..., 0:16]
+    return out
+
+
+def _fault_shift(x, L, y):
+    """BN shift of the weakest channel (smallest max|y|) set to zero."""
+    c = int(np.argmin(np.abs(y.astype(np.float64)).max(axis=(0, 1, 2, 3))))
+    M = copy.copy(L)
+    M.t = L.t.copy()
+    M.t[c] = 0
+    return vc.emulate(x, M)
+
+
+def _fault_partial_brick(x, L, y):
+    """The last, partial brick along x never written: a sentinel stays."""
+    D = y.shape[3]
+    assert D % 8 != 0
+    out = y.copy()
+    out[:, :, :, D // 8 * 8:] = 1234.0
+    return out
+
+
+def _fault_bf16(x, L, y):
+    """Weights rounded to bf16 instead of fp16."""
+    M = copy.copy(L)
+    M.w = _bf16(L.w32)
+    return vc.emulate(x, M)
+
+
+# fault -> the launches it is applied to, per case (0: default layers, R = 32; 1: LIST_A, R = 48), by step index.
+# conv_3_0 (4) is the widest volume; the tile swap needs >= 32 output channels; the partial brick needs a side that is
+# no multiple of 8 (default R = 32: D = 4 at step 10; LIST_A R = 48: D = 12 at step 8); bf16 weights are looked for
+# where they can be seen, at 16 input channels (see the limit in the test below).
+_FAULTS = [(_fault_tap, (4, 6, 10), (4, 6, 8)), (_fault_brick_halo, (4, 6), (4, 6, 8)),
+           (_fault_face_neighbour, (4, 6), (4, 6, 8)), (_fault_tiles, (6, 8), (4, 8)),
+           (_fault_shift, (4, 6, 8), (4, 6, 8)), (_fault_partial_brick, (10,), (8, 9)), (_fault_bf16, (4, 5), (6, 7))]
+
+
+@pytest.mark.parametrize("case", [0, 1])
+def test_per_launch_check_rejects_wrong_layers_and_accepts_the_right_one(case):
+    """Helper A on the inputs of the GPU test.  (1) The converse first: the layer in the device's own precisions
+    (vc.emulate; chained, it IS encode_cpu's fp16 restatement, bit for bit) passes the bound at every element of every
+    launch.  (2) Each deliberately wrong layer is rejected (largest error / bound > 1), on the activations that the
+    right pipeline produces.
+
+    An honest limit: the bound cannot see everything.  A single dropped product among the K = 3456 of a 128-channel
+    layer changes z by about A / K, and the worst-case accumulation term is (K + 2) 2^-23 A = 4e-4 A, about the same;
+    where |y| is not small the fp16 storage term (2^-11 |y|) hides it as well.  bf16 weights at K = 3456 move z by
+    about 2^-9 A / sqrt(3 K) = 2e-5 A and pass for the same reason, which is why that fault is applied at 16 input
+    channels (K = 432, bound 1e-4 A against an expected 5e-5 A per element and several times that at the worst of
+    10^4 elements).  What the check does see is anything that is wrong by more than rounding in even ONE element."""
+    layers, R = (LAYERS, 32) if case == 0 else (vc.LIST_A, 48)
+    m = fill.fill_state(VoxelEncoder2(layers), seed=2).eval()
+    params = voxenc.params_of(m)
+    Ls = vc.launches(params)
+    occ = random_occ(11, 1, R)
+    run = vc.run_emulated(occ, Ls)
+    ref = voxenc.encode_cpu(occ, params, storage="fp16")
+    for k, i in enumerate((2, 4, 6, 8, 10, 12)):
+        assert np.array_equal(np.moveaxis(run[i][1], 4, 1), ref[k]), k
+    for L, (x, y) in zip(Ls, run):
+        q = vc.check(y, x, L)
+        print(f"{L.name:9s} {L.template():12s} the device's arithmetic restated: max error / bound = {q:.3f}")
+        assert q <= 1.0, (L.name, q)
+    for fault, *steps in _FAULTS:
+        for i in steps[case]:
+            L, (x, y) = Ls[i], run[i]
+            q = vc.check(fault(x, L, y), x, L)
+            print(f"{fault.__name__:22s} at {L.name:9s} {L.template():7s} D={x.shape[1]:2d}: max error / bound = {q:.3g}")
+            assert q > 1.0, (fault.__name__, L.name, q)
+
+
+def test_per_launch_check_compares_non_finite_values_by_class():
+    L = vc.launches(voxenc.params_of(fill.fill_state(VoxelEncoder2(LAYERS), seed=2).eval()))[5]      # conv_4: ReLU only
+    x = np.abs(np.random.default_rng(3).standard_normal((1, 6, 6, 6, 16))).astype(np.float16)
+    x[0, 1, 1, 1, 3], x[0, 4, 4, 4, 5] = np.nan, np.inf
+    y = vc.emulate(x, L)
+    assert np.isnan(y[0, 0:3, 0:3, 0:3]).all() and not np.isnan(y[0, 3:, 3:, 3:]).any()
+    assert np.isinf(y[0, 3:, 3:, 3:]).any() and (y[0, 3:, 3:, 3:] == 0).any()     # -inf under the ReLU is 0
+    assert vc.check(y, x, L) <= 1.0
+    for bad in (np.float16(1.0), np.float16(np.inf)):
+        z = y.copy()
+        z[0, 1, 1, 1, 0] = bad                                                    # a NaN lost
+        assert vc.check(z, x, L) == np.inf
+    z = y.copy()
+    z[np.isinf(y)] = np.float16(65504)                                            # an infinity saturated
+    assert vc.check(z, x, L) == np.inf
+    z = y.copy()
+    z[0, 5, 5, 0, 0] = np.nan                                                     # a NaN from nowhere
+    assert vc.check(z, x, L) == np.inf

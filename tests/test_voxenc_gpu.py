@@ -18,6 +18,9 @@ from oracle import fill, synth
 from list_amd import arguments, utils, voxenc
 from list_amd.network.modules import VoxelEncoder2
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _voxenc_check as vc  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -288,3 +291,230 @@ def test_full_size_batch():
         err = float(np.abs(got - want).max())
         print(f"B=8 R=128 level 1, {name} block: max|hip - restatement| = {err:.3e} (bound {HALF_BOUND * top:.3e})")
         assert err <= HALF_BOUND * top
+
+
+# ---- every launch on its own, every element against its own bound (tests/_voxenc_check.py) ---------------------------
+def _occ(kind, B, R, seed=11):
+    if kind == "ones":
+        return np.ones((B, R, R, R), dtype=np.float32)
+    p = {"sparse": 0.03, "dense": 0.5}[kind]
+    return (np.random.default_rng(seed).random((B, R, R, R)) < p).astype(np.float32)
+
+
+def _blocks(D, R, thick, rng):
+    """The blocks [(z0, z1, y0, y1, x0, x1)] of a volume of side D that are checked.  R <= 48 and every level of side
+    <= 24: the whole volume.  Wider levels of R = 80, 96: the first and the last slab of bricks along z over the whole
+    xy extent (two faces, eight edges, all eight corners, and every last brick along x and y) and three seeded
+    8 x 8 x 16 blocks (2 x 2 x 2 bricks) inside.  R = 256: the two 16^3 corner blocks on the diagonal and one inside."""
+    if R <= 48 or D <= 24:
+        return [(0, D, 0, D, 0, D)]
+    if R == 256:
+        o = 16 * int(rng.integers(1, max(D // 16 - 1, 2)))
+        return [(0, 16) * 3, (D - 16, D) * 3, (o, o + 16) * 3]
+    out = [(0, thick, 0, D, 0, D), (D - thick, D, 0, D, 0, D)]
+    for _ in range(3):
+        z, y = (thick + 4 * int(rng.integers(0, (D - 2 * thick - 8) // 4 + 1)) for _ in range(2))
+        x = 8 * int(rng.integers(1, (D - 16) // 8))
+        out.append((z, z + 8, y, y + 8, x, x + 16))
+    return out
+
+
+def _io(step, L, occ, levels, ws, B, R, layers):
+    """(input, output) of launch `step` as device tensors [B,D,D,D,C] (views of the buffers the launch uses)."""
+    n = B * R ** 3
+    cl = lambda v: v.permute(0, 2, 3, 4, 1)
+    t0 = ws[0:4 * n].view(torch.float32).view(B, R, R, R, 1)
+    o1 = voxenc._align(4 * n)
+    t1 = ws[o1:o1 + 4 * n].view(torch.float32).view(B, R, R, R, 1)
+    if step < 3:
+        return (occ.unsqueeze(-1), t0, t1)[step], (t0, t1, cl(levels[0]))[step]
+    mid = cl(voxenc.mid_view(ws, B, R, layers, L.stage))
+    if L.second:
+        return mid, cl(levels[L.stage - 2])
+    return (cl(levels[0]) if L.stage == 3 else cl(voxenc.pooled_view(ws, B, R, layers, L.stage - 1))), mid
+
+
+def _assert_pool(levels, ws, B, R, layers, stage, what):
+    """The fused pool is max_pool3d of the level just written, bit for bit; a window that holds a NaN gives a NaN."""
+    pooled = voxenc.pooled_view(ws, B, R, layers, stage).float()
+    want = torch.nn.functional.max_pool3d(levels[stage - 2].float(), 2)
+    nan = torch.isnan(want)
+    assert torch.equal(torch.isnan(pooled), nan), (what, stage)
+    assert torch.equal(pooled[~nan], want[~nan]), (what, stage)
+    return int(nan.sum())
+
+
+def per_launch(module, occ, what, poke=None, table=None):
+    """Runs the 13 launches one at a time on the device and checks each against the float64 reference of that layer on
+    the device's own input (vc.check), and the fused pool of stages 3 .. 6.  poke(step, ws) may write into the
+    workspace before a launch.  Returns (levels, ws, worst error / bound per launch)."""
+    params = voxenc.params_of(module)
+    layers, Ls = params["layers"], vc.launches(params)
+    B, R = occ.shape[0], occ.shape[1]
+    rng = np.random.default_rng(17)
+    module.to(DEV)
+    try:
+        packed = voxenc.pack(module)
+        d_occ = torch.from_numpy(occ).to(DEV)
+        buffers, worst = None, []
+        for step, L in enumerate(Ls):
+            if buffers is None:
+                levels, ws, buffers = voxenc.encode_steps(d_occ, packed, 0, 0)
+            if poke is not None:
+                poke(step, ws)
+            levels, ws, buffers = voxenc.encode_steps(d_occ, packed, step, step + 1, buffers)
+            torch.cuda.synchronize()
+            x_dev, y_dev = _io(step, L, d_occ, levels, ws, B, R, layers)
+            D = L.D(R)
+            assert x_dev.shape == (B, D, D, D, L.cin) and y_dev.shape == (B, D, D, D, L.cout)
+            q = 0.0
+            for blk in _blocks(D, R, 4 if L.mfma else 8, rng):
+                (za, zb, sz), (ya, yb, sy), (xa, xb, sx) = (vc.crop_range(blk[2 * i], blk[2 * i + 1], D)
+                                                            for i in range(3))
+                x = x_dev[:, za:zb, ya:yb, xa:xb].cpu().numpy()
+                got = y_dev[:, blk[0]:blk[1], blk[2]:blk[3], blk[4]:blk[5]].cpu().numpy()
+                q = max(q, vc.check(got, x, L, inner=(sz, sy, sx)))
+            worst.append(q)
+            print(f"{what}: {L.name:9s} {L.template():12s} D={D:3d}: max error / bound = {q:.3f}")
+            if table is not None:
+                table.append((what, L.name, L.template(), D, q))
+            if L.second and L.stage < voxenc.N_STAGES - 1:
+                _assert_pool(levels, ws, B, R, layers, L.stage, what)
+        assert ws.numel() == voxenc.workspace_bytes(B, R, layers) == voxenc.workspace_bytes_closed_form(B, R, layers)
+        bad = [(L.name, q) for L, q in zip(Ls, worst) if not q <= 1.0]
+        assert not bad, (what, bad)
+        return levels, ws, worst
+    finally:
+        module.cpu()
+
+
+def whole_pipeline(module, occ, what, images=None):
+    """The existing check: the whole forward against the whole restatement (check_levels), on `images` (all)."""
+    params = voxenc.params_of(module)
+    module.to(DEV)
+    try:
+        levels = voxenc.encode(torch.from_numpy(occ).to(DEV), voxenc.pack(module))
+        torch.cuda.synchronize()
+        levels = [v.cpu() for v in levels]
+    finally:
+        module.cpu()
+    sel = slice(None) if images is None else images
+    ref = voxenc.encode_cpu(occ[sel], params, storage="fp16")
+    check_levels([v[sel] for v in levels], ref, what)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("R", [16, 32, 48, 80, 96])
+def test_every_launch_at_every_grid(enc, R, B):
+    """Default layers ([1,1,1,1,16,32,64,128,128]: expand C=16, then <16,1> <16,2> <32,2> <32,4> <32,4> <32,8> x 4) at
+    grids whose levels are single partial bricks (R = 16: 16, 8, 4, 2, 1), powers of two (32), several bricks with a
+    partial last one (R = 48: 48, 24, 12 = 8 + 4, 6 = 4 + 2, 3; R = 80: 80, 40, 20, 10, 5) and R = 96.  R = 16 is
+    accepted by the HIP path (the torch module raises there; test_voxenc_cpu.py) and is checked like every size.
+    The whole-pipeline check runs on every image up to R = 48 and on the last image (the largest image offset) of the
+    two wider grids, where the restatement of three images would cost more than the rest of this file."""
+    occ = _occ("sparse", B, R)
+    per_launch(enc, occ, f"R={R} B={B}")
+    whole_pipeline(enc, occ, f"R={R} B={B}", images=None if R <= 48 else slice(B - 1, B))
+
+
+@pytest.mark.parametrize("layers,R", [(vc.LIST_A, 48), (vc.LIST_B, 32)])
+def test_every_launch_of_other_architectures(layers, R):
+    """The instantiations and widths the default network never reaches, launch by launch (conv_3 .. conv_7_0):
+      [1,1,1,1,64,16,128,16,64], R = 48: expand C=64, <32,4> | <32,1> <16,1> | <16,8> <32,8> | <32,1> <16,1> |
+                                          <16,4> <32,4>            -- first runs of <32,1>, <16,8>, <16,4>
+      [1,1,1,1,128,128,32,16,16], R = 32: expand C=128 (its LDS limit), <32,8> | <32,8> <32,8> | <32,2> <32,2> |
+                                          <32,1> <16,1> | <16,1> <16,1>   -- a 128-channel level 1."""
+    m = fill.fill_state(VoxelEncoder2(layers), seed=2).eval()
+    occ = _occ("sparse", 1, R)
+    per_launch(m, occ, f"layers={layers[4:]} R={R}")
+    whole_pipeline(m, occ, f"layers={layers[4:]} R={R}")
+
+
+@pytest.mark.parametrize("R", [32, 48])
+@pytest.mark.parametrize("kind", ["ones", "dense"])
+def test_every_launch_on_full_halos(enc, kind, R):
+    """All ones and dense random (p = 0.5) occupancy: every halo voxel is non-zero, so a brick halo that reads zero
+    where the neighbouring brick has data, or data where the volume ends, is an error of order one."""
+    occ = _occ(kind, 1, R)
+    per_launch(enc, occ, f"{kind} R={R}")
+    whole_pipeline(enc, occ, f"{kind} R={R}")
+
+
+def _signed_bn(layers, seed):
+    """fill_state, then BN scales of both signs with exact zeros among them and shifts of both signs (seeded)."""
+    m = fill.fill_state(VoxelEncoder2(layers), seed=2).eval()
+    rng = np.random.default_rng(seed)
+    with torch.no_grad():
+        for bn in m.bn:
+            n = bn.weight.numel()
+            w = rng.uniform(0.5, 1.5, n) * rng.choice([-1.0, 1.0], n)
+            if n > 1:
+                w[rng.choice(n, max(n // 8, 1), replace=False)] = 0.0
+            bn.weight.copy_(torch.from_numpy(w.astype(np.float32)))
+            bn.bias.copy_(torch.from_numpy(rng.uniform(-0.3, 0.3, n).astype(np.float32)))
+    return m
+
+
+def test_every_launch_with_negative_and_zero_bn_scales():
+    """ReLU, THEN the affine: a negative scale gives negative activations (the pool is over negative values, the next
+    convolution reads them), a zero scale a constant channel."""
+    m = _signed_bn(LAYERS, 23)
+    assert any((bn.weight < 0).any() and (bn.weight == 0).any() for bn in m.bn[3:])
+    occ = _occ("sparse", 2, 32, seed=12)
+    levels, _, _ = per_launch(m, occ, "signed BN R=32 B=2")
+    assert all(float(v.float().min()) < 0 for v in levels[1:])
+    whole_pipeline(m, occ, "signed BN R=32 B=2")
+
+
+def test_non_finite_activations_propagate_as_in_the_reference(enc):
+    """A NaN and a +inf written into the pooled output of stage 3 (the fp16 input of conv_4) between two launches:
+    only the device sees them.  Per launch the non-finite classes must be those of the float64 reference (vc.ratios);
+    at conv_4 that is: NaN at exactly the 3^3 neighbourhood of the NaN voxel, in every channel; around the +inf voxel
+    +inf where the tap's weight is positive and relu(-inf) = 0 where it is negative.  The fused pools return NaN for
+    every window that holds one, as max_pool3d does (_assert_pool)."""
+    R, at_nan, at_inf = 32, (3, 0, 8), (9, 12, 7)              # voxels of the 16^3 pooled volume: a face and inside
+
+    def poke(step, ws):
+        if step == 5:
+            v = voxenc.pooled_view(ws, 1, R, LAYERS, 3)
+            v[0, 5, at_nan[0], at_nan[1], at_nan[2]] = float("nan")
+            v[0, 9, at_inf[0], at_inf[1], at_inf[2]] = float("inf")
+    levels, ws, _ = per_launch(enc, _occ("sparse", 1, R), "non-finite R=32", poke=poke)
+    lvl2 = levels[2].float().cpu().numpy()[0]                  # [C,16,16,16]: two launches after the poke
+    assert np.isnan(lvl2).any() and np.isfinite(lvl2).any()
+    near = np.zeros((16, 16, 16), dtype=bool)
+    for z, y, x in (at_nan, at_inf):
+        near[max(z - 2, 0):z + 3, max(y - 2, 0):y + 3, max(x - 2, 0):x + 3] = True
+    assert np.isfinite(lvl2[:, ~near]).all()                   # two 3^3 convolutions: nothing beyond 5^3
+    nan5 = np.zeros((16, 16, 16), dtype=bool)
+    z, y, x = at_nan
+    nan5[max(z - 2, 0):z + 3, max(y - 2, 0):y + 3, max(x - 2, 0):x + 3] = True
+    assert np.isnan(lvl2[:, nan5]).all()
+    assert torch.isnan(voxenc.pooled_view(ws, 1, R, LAYERS, 4)).any()
+
+
+def test_fp16_overflow_gives_infinity_not_saturation():
+    """conv_3 (fp32 weights) and conv_3_0 scaled so that level 1 passes 65504: the output holds +inf where the
+    reference rounded to fp16 does (include/list_voxenc.h: not saturated), and the later launches, which now read
+    infinities, agree with the reference by class."""
+    m = fill.fill_state(VoxelEncoder2(LAYERS), seed=2).eval()
+    with torch.no_grad():
+        m.conv["conv_3"].weight.mul_(2000.0)
+        m.conv["conv_3_0"].weight.mul_(80.0)
+    assert float(m.conv["conv_3_0"].weight.abs().max()) < 60000    # the fp16 weights themselves stay finite
+    levels, _, _ = per_launch(m, _occ("sparse", 1, 32), "overflow R=32")
+    lvl1 = levels[1].float()
+    n_inf = int(torch.isinf(lvl1).sum())
+    print(f"overflow R=32: {n_inf} of {lvl1.numel()} elements of level 1 are infinite")
+    assert n_inf > 0 and not torch.isnan(lvl1).any() and float(lvl1[torch.isfinite(lvl1)].max()) > 4096
+
+
+def test_every_launch_at_the_largest_grid(enc):
+    """R = 256 = LIST_VOXENC_MAX_R, B = 1 (the workspace is about 0.8 GiB): finite outputs, buffer sizes equal to
+    their closed forms (per_launch asserts it), the fused pools over the whole volumes, and the per-launch check on
+    the two corner blocks of the diagonal and one interior block of every launch."""
+    occ = _occ("sparse", 1, 256)
+    levels, ws, _ = per_launch(enc, occ, "R=256 B=1")
+    assert ws.numel() == voxenc.workspace_bytes_closed_form(1, 256, LAYERS) == 725 << 20
+    for k, v in enumerate(levels):
+        assert v.shape[2] == 256 >> max(k - 1, 0) and torch.isfinite(v).all(), k
