@@ -13,7 +13,6 @@ bits.  Every `*_cpu` function is the header's contract restated in numpy: the te
                                path (network.executors.chamfer_distance) on CPU tensors.
 """
 import ctypes as C
-import threading
 
 import numpy as np
 import torch
@@ -31,27 +30,8 @@ LOSS_EXPORTS = {
 SERIAL_MAX = 32             # list_loss.h: a target with more sources than this is summed by a whole wave
 _RED_LANES = 256            # list_loss.h: lanes of the per-batch float64 sum
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """The liblist_hip.so of hip.load(), with the symbols of include/list_loss.h bound."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                lib = hip.load()
-                for name, (res, args) in LOSS_EXPORTS.items():
-                    fn = getattr(lib, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = lib
-    return _lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise hip.ListError(what, rc, load().list_loss_last_error().decode("utf-8", "replace"))
+_section = hip.Section(LOSS_EXPORTS, "list_loss_last_error")    # include/list_loss.h on hip.load()'s handle
+load, _check = _section.load, _section.check
 
 
 def _validate(x, y):
@@ -80,10 +60,7 @@ def _fwd(x, y):
     idx_yx = torch.empty((B, M), dtype=torch.int32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        need = lib.list_chamfer_workspace_bytes(B, N, M)
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_chamfer_workspace_bytes")
-        ws = hip._workspace(dev, need)
+        ws = _section.workspace(dev, lib.list_chamfer_workspace_bytes(B, N, M), "list_chamfer_workspace_bytes")
         _check(lib.list_chamfer_fwd(x.data_ptr(), y.data_ptr(), B, N, M, d2_xy.data_ptr(), idx_xy.data_ptr(),
                                     d2_yx.data_ptr(), idx_yx.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(),
                                     hip._stream()), "list_chamfer_fwd")
@@ -98,10 +75,7 @@ def _bwd(x, y, idx_xy, idx_yx, grad_loss, want_x, want_y):
     gx = torch.empty_like(x) if want_x else None
     gy = torch.empty_like(y) if want_y else None
     with torch.cuda.device(dev):
-        need = lib.list_chamfer_workspace_bytes(B, N, M)
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_chamfer_workspace_bytes")
-        ws = hip._workspace(dev, need)
+        ws = _section.workspace(dev, lib.list_chamfer_workspace_bytes(B, N, M), "list_chamfer_workspace_bytes")
         _check(lib.list_chamfer_bwd(x.data_ptr(), y.data_ptr(), B, N, M, idx_xy.data_ptr(), idx_yx.data_ptr(),
                                     g.data_ptr(), gx.data_ptr() if want_x else None,
                                     gy.data_ptr() if want_y else None, ws.data_ptr(), ws.numel(), hip._stream()),

@@ -8,31 +8,15 @@
 //   fps_kernel<P>         one workgroup per cloud, P points per lane: running minima in registers, argmax per step
 //                         over the wave (shuffles) and then over the waves (LDS).
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <hip/hip_runtime.h>
 
 #include "list_data.h"
+#include "list_host.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-thread_local char g_data_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_data_err, sizeof(g_data_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LIST_OK : fail(LIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
 
 // ---- signed distance --------------------------------------------------------------------------------------------------
 constexpr int kThreads = 256;
@@ -341,7 +325,7 @@ void launch_fps(const float* clouds, int64_t B, int32_t N, int32_t K, int32_t* i
 
 extern "C" {
 
-const char* list_data_last_error(void) { return g_data_err; }
+const char* list_data_last_error(void) { return g_err; }
 
 size_t list_data_signed_distance_workspace_bytes(int64_t n_faces) {
   if (n_faces <= 0 || n_faces > INT32_MAX) {
@@ -364,8 +348,7 @@ int list_data_signed_distance(const float* verts, int64_t n_verts, const int32_t
   if (n_points && (!points || !sdf || !face_idx)) return fail(LIST_ERR_ARG, "points/sdf/face_idx is NULL");
   const size_t need = (size_t)n_faces * sizeof(FacePrep);
   if (workspace_bytes < need)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_data_signed_distance_workspace_bytes)",
-                workspace_bytes, need);
+    return workspace_too_small(workspace_bytes, need, "list_data_signed_distance_workspace_bytes");
   if (n_points == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
   FacePrep* prep = (FacePrep*)workspace;

@@ -10,29 +10,16 @@
 //   hipCUB radix sort      (key, face) pairs: the CSR of the res^2 cells;  cell_offsets_kernel: first entry per cell.
 //   contains_kernel        per point: parity of the hits over every triangle whose cell bbox covers its cell.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include "list_eval.h"
+#include "list_host.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-thread_local char g_eval_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_eval_err, sizeof(g_eval_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ bool face_ok(const int32_t* __restrict__ faces, int64_t f, int64_t V, int32_t c[3]) {
   c[0] = faces[3 * f];
@@ -460,22 +447,11 @@ bool contains_layout(int64_t F, int32_t res, ContainsLayout* L) {
   return true;
 }
 
-const char* faces_error(int64_t V, int64_t F) {
-  static thread_local char msg[160];
-  if (F <= 0 || F > INT32_MAX) {
-    snprintf(msg, sizeof(msg), "%lld faces: need 1 <= F <= INT32_MAX", (long long)F);
-    return msg;
-  }
-  if (V <= 0 || V > INT32_MAX) {
-    snprintf(msg, sizeof(msg), "%lld vertices: need 1 <= V <= INT32_MAX", (long long)V);
-    return msg;
-  }
-  return nullptr;
-}
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LIST_OK : fail(LIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+// LIST_OK, or a refusal with its message
+int check_faces(int64_t V, int64_t F) {
+  if (F <= 0 || F > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld faces: need 1 <= F <= INT32_MAX", (long long)F);
+  if (V <= 0 || V > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld vertices: need 1 <= V <= INT32_MAX", (long long)V);
+  return LIST_OK;
 }
 
 unsigned blocks(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
@@ -484,7 +460,7 @@ unsigned blocks(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 extern "C" {
 
-const char* list_eval_last_error(void) { return g_eval_err; }
+const char* list_eval_last_error(void) { return g_err; }
 
 int list_eval_nn(const float* src, int64_t n_src, const float* dst, int64_t n_dst, float* dist, int32_t* idx,
                  void* stream) {
@@ -522,15 +498,14 @@ size_t list_eval_sample_workspace_bytes(int64_t n_faces) {
 int list_eval_sample(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int64_t n_samples,
                      uint64_t seed, void* workspace, size_t workspace_bytes, float* points, int32_t* face_idx,
                      void* stream) {
-  if (const char* m = faces_error(n_verts, n_faces)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_faces(n_verts, n_faces)) return rc;
   if (n_samples < 0 || n_samples > INT32_MAX) return fail(LIST_ERR_SHAPE, "n = %lld samples", (long long)n_samples);
   if (!verts || !faces || !workspace) return fail(LIST_ERR_ARG, "verts/faces/workspace is NULL");
   if (n_samples && (!points || !face_idx)) return fail(LIST_ERR_ARG, "points/face_idx is NULL");
   SampleLayout L;
   if (!sample_layout(n_faces, &L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::InclusiveSum: scratch size query failed");
   if (workspace_bytes < L.total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_eval_sample_workspace_bytes)",
-                workspace_bytes, L.total);
+    return workspace_too_small(workspace_bytes, L.total, "list_eval_sample_workspace_bytes");
   if (n_samples == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -541,7 +516,7 @@ int list_eval_sample(const float* verts, int64_t n_verts, const int32_t* faces, 
   if (int rc = launched("face_area_kernel")) return rc;
   size_t scratch = L.scratch_bytes;
   hipError_t e = hipcub::DeviceScan::InclusiveSum(ws + L.scratch, scratch, area, cdf, (int)n_faces, s);
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::InclusiveSum: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceScan::InclusiveSum");
   hipLaunchKernelGGL(sample_kernel, dim3(blocks(n_samples)), dim3(kThreads), 0, s, verts, n_verts, faces, n_faces, cdf,
                      n_samples, splitmix64(seed), points, face_idx);
   return launched("sample_kernel");
@@ -567,7 +542,7 @@ size_t list_eval_contains_workspace_bytes(int64_t n_faces, int32_t hash_res) {
 int list_eval_contains(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
                        const double* points, int64_t n_points, const double* rot, int32_t hash_res, void* workspace,
                        size_t workspace_bytes, uint8_t* flags, void* stream) {
-  if (const char* m = faces_error(n_verts, n_faces)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_faces(n_verts, n_faces)) return rc;
   if (hash_res < 1 || hash_res > LIST_EVAL_MAX_HASH_RES)
     return fail(LIST_ERR_SHAPE, "hash_res %d: need 1 <= res <= %d", hash_res, LIST_EVAL_MAX_HASH_RES);
   if (n_points < 0 || n_points > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld points", (long long)n_points);
@@ -577,8 +552,7 @@ int list_eval_contains(const float* verts, int64_t n_verts, const int32_t* faces
   if (!contains_layout(n_faces, hash_res, &L))
     return fail(LIST_ERR_HIP, "hipcub::DeviceRadixSort::SortPairs: scratch size query failed");
   if (workspace_bytes < L.total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_eval_contains_workspace_bytes)",
-                workspace_bytes, L.total);
+    return workspace_too_small(workspace_bytes, L.total, "list_eval_contains_workspace_bytes");
   if (n_points == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -605,7 +579,7 @@ int list_eval_contains(const float* verts, int64_t n_verts, const int32_t* faces
   size_t scratch = L.scratch_bytes;
   hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.scratch, scratch, keys_in, keys_out, vals_in, vals_out,
                                                     (int)F, 0, L.key_bits, s);
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "hipcub::DeviceRadixSort::SortPairs: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceRadixSort::SortPairs");
   hipLaunchKernelGGL(cell_offsets_kernel, dim3(blocks(L.n_off)), dim3(kThreads), 0, s, keys_out, F, L.n_off, offsets);
   if (int rc = launched("cell_offsets_kernel")) return rc;
   hipLaunchKernelGGL(contains_kernel, dim3(blocks(n_points)), dim3(kThreads), 0, s, points, n_points, rot,

@@ -1,28 +1,13 @@
 // C ABI (include/list_hip.h): argument validation, workspace carving, launch sequencing.
 // No allocation, no synchronisation, no global mutable state (thread-local error text only).
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "list_common.h"
+#include "list_host.h"
 
 using namespace list;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(LIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
 
 constexpr int64_t kMaxChunkRows = 262144;     // bounds the workspace (~4.6 GB) for huge queries
 

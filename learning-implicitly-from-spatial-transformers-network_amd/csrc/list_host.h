@@ -1,0 +1,43 @@
+// Host-side plumbing shared by the translation units of the C ABI (list_capi.hip and the *_kernels.hip files that
+// export a section of their own).  Not part of the C ABI.
+//
+// Everything here is static: each unit that includes this header gets its OWN thread-local error text, the
+// one its list_*_last_error() returns -- a failing Chamfer call leaves list_mesh_last_error() as it was.
+#pragma once
+
+#include <stdarg.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <hip/hip_runtime.h>
+
+#include "list_hip.h"
+
+static thread_local char g_err[512] = "";
+
+// Sets this unit's error text and returns `code`: `return fail(LIST_ERR_ARG, "x is NULL");`
+__attribute__((format(printf, 2, 3))) static int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+static int hip_fail(hipError_t e, const char* what) { return fail(LIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); }
+
+// After a kernel launch: LIST_OK, or the launch error under the kernel's name
+static int launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? LIST_OK : hip_fail(e, what);
+}
+
+// Refusal of a workspace smaller than `sizing_fn` (the section's list_*_workspace_bytes) asks for
+static int workspace_too_small(size_t have, size_t need, const char* sizing_fn) {
+  return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (%s)", have, need, sizing_fn);
+}
+
+static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace regions start on 256 bytes
+
+static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -15,33 +15,15 @@
 //                       sources is summed by the whole wave).
 #include <limits.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <hip/hip_runtime.h>
 
+#include "list_host.h"
 #include "list_loss.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-thread_local char g_loss_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_loss_err, sizeof(g_loss_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LIST_OK : fail(LIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 typedef float float2v __attribute__((ext_vector_type(2)));
 
@@ -381,8 +363,6 @@ struct Layout {
   size_t packed, partial, cnt[2], end[2], ord[2], total;
 };
 
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 FwdGrid fwd_grid(int64_t B, int64_t N, int64_t M) {
   return FwdGrid{B, N, M, cdiv(N, kSrc), cdiv(M, kChunk), cdiv(M, kSrc), cdiv(N, kChunk)};
 }
@@ -422,7 +402,7 @@ Layout layout(int64_t B, int64_t N, int64_t M) {
 
 extern "C" {
 
-const char* list_loss_last_error(void) { return g_loss_err; }
+const char* list_loss_last_error(void) { return g_err; }
 
 size_t list_chamfer_workspace_bytes(int64_t B, int64_t N, int64_t M) {
   if (check_shape(B, N, M) != LIST_OK) return 0;
@@ -436,15 +416,13 @@ int list_chamfer_fwd(const float* x, const float* y, int64_t B, int64_t N, int64
   if (!x || !y || !d2_xy || !idx_xy || !d2_yx || !idx_yx || !loss || !workspace)
     return fail(LIST_ERR_ARG, "x/y/d2_xy/idx_xy/d2_yx/idx_yx/loss/workspace is NULL");
   const Layout L = layout(B, N, M);
-  if (workspace_bytes < L.total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_chamfer_workspace_bytes)", workspace_bytes,
-                L.total);
+  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_chamfer_workspace_bytes");
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   unsigned long long* packed = (unsigned long long*)(ws + L.packed);
   double* partial = (double*)(ws + L.partial);
   hipError_t e = hipMemsetAsync(packed, 0xFF, (size_t)(B * (N + M)) * sizeof(unsigned long long), s);
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
   const FwdGrid g = fwd_grid(B, N, M);
   hipLaunchKernelGGL(nn_sq_kernel, dim3((unsigned)(B * (g.sx * g.tx + g.sy * g.ty))), dim3(kFwdThreads), 0, s, x, y,
                      g, packed);
@@ -464,9 +442,7 @@ int list_chamfer_bwd(const float* x, const float* y, int64_t B, int64_t N, int64
     return fail(LIST_ERR_ARG, "x/y/idx_xy/idx_yx/grad_loss/workspace is NULL");
   if (!grad_x && !grad_y) return fail(LIST_ERR_ARG, "grad_x and grad_y are both NULL");
   const Layout L = layout(B, N, M);
-  if (workspace_bytes < L.total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_chamfer_workspace_bytes)", workspace_bytes,
-                L.total);
+  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_chamfer_workspace_bytes");
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   const bool want[2] = {grad_x != nullptr, grad_y != nullptr};
@@ -478,7 +454,7 @@ int list_chamfer_bwd(const float* x, const float* y, int64_t B, int64_t N, int64
   for (int k = 0; k < 2; ++k) {
     if (!want[k]) continue;
     const hipError_t e = hipMemsetAsync(side[k].count, 0, (size_t)(B * side[k].T) * sizeof(int32_t), s);
-    if (e != hipSuccess) return fail(LIST_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
     a.side[a.nsides] = side[k];
     a.hist_blocks[a.nsides] = cdiv(B * side[k].S, kHistThreads);
     ++a.nsides;

@@ -7,26 +7,14 @@
 //   mc_totals_kernel  V and F into the caller's device int64[2].
 //   mc_emit_kernel    per point with something to write: its vertices, and its cell's triangles, whose vertex numbers
 //                     come from the scan and the masks of the points owning the cell's edges.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "list_host.h"
 #include "list_mesh.h"
 #include "mc_tables.h"
 
 namespace {
-
-thread_local char g_mesh_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_mesh_err, sizeof(g_mesh_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
 
 // count tile: 64 points along axis 2 (one wave) x 8 along axis 1, marching over 16 slices of axis 0
 constexpr int kTK = 64, kTJ = 8, kTI = 16;
@@ -162,23 +150,17 @@ __global__ __launch_bounds__(kEmitThreads) void mc_emit_kernel(
 }
 
 // ---- workspace: counts u64 [N] | offsets u64 [N] | info u16 [N] | scan scratch ----
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
   size_t counts, offsets, info, scratch, scratch_bytes, total;
 };
 
-const char* shape_error(int32_t X, int32_t Y, int32_t Z) {
-  static thread_local char msg[160];
-  if (X < 2 || Y < 2 || Z < 2) {
-    snprintf(msg, sizeof(msg), "volume %d x %d x %d: every axis must be >= 2", X, Y, Z);
-    return msg;
-  }
-  if (3 * (int64_t)X * Y * Z > INT32_MAX) {
-    snprintf(msg, sizeof(msg), "volume %d x %d x %d: 3 * X * Y * Z exceeds INT32_MAX", X, Y, Z);
-    return msg;
-  }
-  return nullptr;
+// LIST_OK, or a refusal with its message
+int check_shape(int32_t X, int32_t Y, int32_t Z) {
+  if (X < 2 || Y < 2 || Z < 2)
+    return fail(LIST_ERR_SHAPE, "volume %d x %d x %d: every axis must be >= 2", X, Y, Z);
+  if (3 * (int64_t)X * Y * Z > INT32_MAX)
+    return fail(LIST_ERR_SHAPE, "volume %d x %d x %d: 3 * X * Y * Z exceeds INT32_MAX", X, Y, Z);
+  return LIST_OK;
 }
 
 bool layout(int32_t X, int32_t Y, int32_t Z, Layout* L) {
@@ -200,13 +182,10 @@ bool layout(int32_t X, int32_t Y, int32_t Z, Layout* L) {
 
 extern "C" {
 
-const char* list_mesh_last_error(void) { return g_mesh_err; }
+const char* list_mesh_last_error(void) { return g_err; }
 
 size_t list_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (const char* m = shape_error(X, Y, Z)) {
-    fail(LIST_ERR_SHAPE, "%s", m);
-    return 0;
-  }
+  if (check_shape(X, Y, Z) != LIST_OK) return 0;
   Layout L;
   if (!layout(X, Y, Z, &L)) {
     fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
@@ -217,13 +196,11 @@ size_t list_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z) {
 
 int list_mc_count(const float* volume, int32_t X, int32_t Y, int32_t Z, float level, void* workspace,
                   size_t workspace_bytes, int64_t* totals, void* stream) {
-  if (const char* m = shape_error(X, Y, Z)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_shape(X, Y, Z)) return rc;
   if (!volume || !workspace || !totals) return fail(LIST_ERR_ARG, "volume/workspace/totals is NULL");
   Layout L;
   if (!layout(X, Y, Z, &L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-  if (workspace_bytes < L.total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_mc_workspace_bytes)", workspace_bytes,
-                L.total);
+  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_mc_workspace_bytes");
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   uint64_t* counts = (uint64_t*)(ws + L.counts);
@@ -231,22 +208,19 @@ int list_mc_count(const float* volume, int32_t X, int32_t Y, int32_t Z, float le
   uint16_t* info = (uint16_t*)(ws + L.info);
   const dim3 grid((Z + kTK - 1) / kTK, (Y + kTJ - 1) / kTJ, (X + kTI - 1) / kTI);
   hipLaunchKernelGGL(mc_count_kernel, grid, dim3(kTK, kTJ), 0, s, volume, X, Y, Z, level, counts, info);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "mc_count_kernel: %s", hipGetErrorString(e));
+  if (int rc = launched("mc_count_kernel")) return rc;
   const int64_t N = (int64_t)X * Y * Z;
   size_t scratch = L.scratch_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, counts, offsets, (int)N, s);
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: %s", hipGetErrorString(e));
+  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, counts, offsets, (int)N, s);
+  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceScan::ExclusiveSum");
   hipLaunchKernelGGL(mc_totals_kernel, dim3(1), dim3(1), 0, s, counts, offsets, N - 1, totals);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "mc_totals_kernel: %s", hipGetErrorString(e));
-  return LIST_OK;
+  return launched("mc_totals_kernel");
 }
 
 int list_mc_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float level, const float bb_min[3],
                  const float bb_max[3], const void* workspace, size_t workspace_bytes, float* verts, int64_t n_verts,
                  int32_t* faces, int64_t n_faces, void* stream) {
-  if (const char* m = shape_error(X, Y, Z)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_shape(X, Y, Z)) return rc;
   if (!volume || !workspace || !bb_min || !bb_max) return fail(LIST_ERR_ARG, "volume/workspace/bb_min/bb_max is NULL");
   if (n_verts < 0 || n_faces < 0) return fail(LIST_ERR_ARG, "n_verts=%lld n_faces=%lld", (long long)n_verts,
                                               (long long)n_faces);
@@ -255,9 +229,7 @@ int list_mc_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float lev
   if ((n_verts && !verts) || (n_faces && !faces)) return fail(LIST_ERR_ARG, "verts/faces is NULL");
   Layout L;
   if (!layout(X, Y, Z, &L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-  if (workspace_bytes < L.total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_mc_workspace_bytes)", workspace_bytes,
-                L.total);
+  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_mc_workspace_bytes");
   if (n_verts == 0 && n_faces == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
   const int dims[3] = {X, Y, Z};
@@ -269,9 +241,7 @@ int list_mc_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float lev
                      s, volume, X, Y, Z, level, bb_min[0], bb_min[1], bb_min[2], scale[0], scale[1], scale[2],
                      (const uint64_t*)(ws + L.offsets), (const uint16_t*)(ws + L.info), verts, n_verts, faces,
                      n_faces);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "mc_emit_kernel: %s", hipGetErrorString(e));
-  return LIST_OK;
+  return launched("mc_emit_kernel");
 }
 
 }  // extern "C"

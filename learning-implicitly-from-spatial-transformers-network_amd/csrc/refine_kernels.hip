@@ -10,25 +10,13 @@
 //   refine_emit_kernel      one thread per fine point: a refined point writes its coordinates and flat index.
 //   refine_fill_kernel      one thread per fine point: lattice value, refined value or trilinear interpolation.
 // No atomics: every output element has exactly one writer, so the results are deterministic.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "list_host.h"
 #include "list_refine.h"
 
 namespace {
-
-thread_local char g_refine_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_refine_err, sizeof(g_refine_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
 
 constexpr int kThreads = 256;
 
@@ -189,27 +177,17 @@ __global__ __launch_bounds__(kThreads) void refine_fill_kernel(const float* __re
 }
 
 // ---- workspace: active u8 [NB^3] | dilated u8 [NB^3] | flags u32 [R^3] | offsets u32 [R^3] | scan scratch ----
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
   size_t active, dilated, flags, offsets, scratch, scratch_bytes, total;
 };
 
-const char* shape_error(int32_t R, int32_t s) {
-  static thread_local char msg[192];
-  if (s != 2 && s != 4 && s != 8) {
-    snprintf(msg, sizeof(msg), "stride s = %d: must be 2, 4 or 8", s);
-    return msg;
-  }
-  if (R < 2) {
-    snprintf(msg, sizeof(msg), "R = %d: the grid needs at least 2 points per axis", R);
-    return msg;
-  }
-  if (R > LIST_REFINE_MAX_R) {
-    snprintf(msg, sizeof(msg), "R = %d: R^3 exceeds INT32_MAX (at most R = %d)", R, LIST_REFINE_MAX_R);
-    return msg;
-  }
-  return nullptr;
+// LIST_OK, or a refusal with its message
+int check_shape(int32_t R, int32_t s) {
+  if (s != 2 && s != 4 && s != 8) return fail(LIST_ERR_SHAPE, "stride s = %d: must be 2, 4 or 8", s);
+  if (R < 2) return fail(LIST_ERR_SHAPE, "R = %d: the grid needs at least 2 points per axis", R);
+  if (R > LIST_REFINE_MAX_R)
+    return fail(LIST_ERR_SHAPE, "R = %d: R^3 exceeds INT32_MAX (at most R = %d)", R, LIST_REFINE_MAX_R);
+  return LIST_OK;
 }
 
 bool layout(int32_t R, int32_t s, Layout* L) {
@@ -231,12 +209,10 @@ bool layout(int32_t R, int32_t s, Layout* L) {
 
 // shared checks of the entry points that take a workspace
 int check_ws(int32_t R, int32_t s, const void* workspace, size_t workspace_bytes, Layout* L) {
-  if (const char* m = shape_error(R, s)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_shape(R, s)) return rc;
   if (!workspace) return fail(LIST_ERR_ARG, "workspace is NULL");
   if (!layout(R, s, L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-  if (workspace_bytes < L->total)
-    return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (list_refine_workspace_bytes)", workspace_bytes,
-                L->total);
+  if (workspace_bytes < L->total) return workspace_too_small(workspace_bytes, L->total, "list_refine_workspace_bytes");
   return LIST_OK;
 }
 
@@ -246,13 +222,10 @@ unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads
 
 extern "C" {
 
-const char* list_refine_last_error(void) { return g_refine_err; }
+const char* list_refine_last_error(void) { return g_err; }
 
 size_t list_refine_workspace_bytes(int32_t R, int32_t s) {
-  if (const char* m = shape_error(R, s)) {
-    fail(LIST_ERR_SHAPE, "%s", m);
-    return 0;
-  }
+  if (check_shape(R, s) != LIST_OK) return 0;
   Layout L;
   if (!layout(R, s, &L)) {
     fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
@@ -262,17 +235,14 @@ size_t list_refine_workspace_bytes(int32_t R, int32_t s) {
 }
 
 size_t list_refine_mask_offset(int32_t R, int32_t s) {
-  if (const char* m = shape_error(R, s)) {
-    fail(LIST_ERR_SHAPE, "%s", m);
-    return 0;
-  }
+  if (check_shape(R, s) != LIST_OK) return 0;
   const Dims d = dims_of(R, s);
   return align_up((size_t)d.NB * d.NB * d.NB);
 }
 
 int list_refine_count(const float* lattice, int32_t R, int32_t s, float level, float band, void* workspace,
                       size_t workspace_bytes, int64_t* total, void* stream) {
-  if (const char* m = shape_error(R, s)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_shape(R, s)) return rc;
   if (!lattice || !total) return fail(LIST_ERR_ARG, "lattice/total is NULL");
   if (!isfinite(level)) return fail(LIST_ERR_ARG, "level = %g: must be finite", (double)level);
   if (!(band >= 0.f) || !isfinite(band)) return fail(LIST_ERR_ARG, "band = %g: must be finite and >= 0", (double)band);
@@ -288,26 +258,21 @@ int list_refine_count(const float* lattice, int32_t R, int32_t s, float level, f
   const int64_t nb3 = (int64_t)d.NB * d.NB * d.NB, N = (int64_t)R * R * R;
   hipLaunchKernelGGL(refine_classify_kernel, dim3(blocks_for(nb3)), dim3(kThreads), 0, st, lattice, d, level, band,
                      active);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "refine_classify_kernel: %s", hipGetErrorString(e));
+  if (int rc = launched("refine_classify_kernel")) return rc;
   hipLaunchKernelGGL(refine_dilate_kernel, dim3(blocks_for(nb3)), dim3(kThreads), 0, st, active, d, dilated);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "refine_dilate_kernel: %s", hipGetErrorString(e));
+  if (int rc = launched("refine_dilate_kernel")) return rc;
   hipLaunchKernelGGL(refine_flag_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, st, dilated, d, flags);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "refine_flag_kernel: %s", hipGetErrorString(e));
+  if (int rc = launched("refine_flag_kernel")) return rc;
   size_t scratch = L.scratch_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, flags, offsets, (int)N, st);
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: %s", hipGetErrorString(e));
+  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, flags, offsets, (int)N, st);
+  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceScan::ExclusiveSum");
   hipLaunchKernelGGL(refine_total_kernel, dim3(1), dim3(1), 0, st, flags, offsets, N - 1, total);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "refine_total_kernel: %s", hipGetErrorString(e));
-  return LIST_OK;
+  return launched("refine_total_kernel");
 }
 
 int list_refine_emit(int32_t R, int32_t s, double lo, double hi, const void* workspace, size_t workspace_bytes,
                      float* coords, int32_t* indices, int64_t n, void* stream) {
-  if (const char* m = shape_error(R, s)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_shape(R, s)) return rc;
   if (!isfinite(lo) || !isfinite(hi)) return fail(LIST_ERR_ARG, "lo = %g, hi = %g: must be finite", lo, hi);
   if (n < 0) return fail(LIST_ERR_ARG, "n = %lld", (long long)n);
   if (n > (int64_t)R * R * R) return fail(LIST_ERR_ARG, "n = %lld exceeds R^3", (long long)n);
@@ -321,14 +286,12 @@ int list_refine_emit(int32_t R, int32_t s, double lo, double hi, const void* wor
   hipLaunchKernelGGL(refine_emit_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, (hipStream_t)stream,
                      (const uint32_t*)(ws + L.flags), (const uint32_t*)(ws + L.offsets), R, lo, hi, step, coords,
                      indices, n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "refine_emit_kernel: %s", hipGetErrorString(e));
-  return LIST_OK;
+  return launched("refine_emit_kernel");
 }
 
 int list_refine_fill(const float* lattice, const float* values, int64_t n, int32_t R, int32_t s,
                      const void* workspace, size_t workspace_bytes, float* volume, void* stream) {
-  if (const char* m = shape_error(R, s)) return fail(LIST_ERR_SHAPE, "%s", m);
+  if (int rc = check_shape(R, s)) return rc;
   if (!lattice || !volume) return fail(LIST_ERR_ARG, "lattice/volume is NULL");
   if (n < 0) return fail(LIST_ERR_ARG, "n = %lld", (long long)n);
   if (n && !values) return fail(LIST_ERR_ARG, "values is NULL");
@@ -339,9 +302,7 @@ int list_refine_fill(const float* lattice, const float* values, int64_t n, int32
   hipLaunchKernelGGL(refine_fill_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, (hipStream_t)stream, lattice,
                      values, n, (const uint32_t*)(ws + L.flags), (const uint32_t*)(ws + L.offsets), dims_of(R, s),
                      volume);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(LIST_ERR_HIP, "refine_fill_kernel: %s", hipGetErrorString(e));
-  return LIST_OK;
+  return launched("refine_fill_kernel");
 }
 
 }  // extern "C"

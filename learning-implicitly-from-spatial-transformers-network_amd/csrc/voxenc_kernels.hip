@@ -13,25 +13,13 @@
 //                           2x2x2 max-pooled brick from the same LDS image.
 //   voxenc_pack_kernel ...  the prep of list_voxenc_prep_weights.
 // fp16 outputs are not saturated (a non-finite activation propagates).  No atomics: one writer per output element.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <hip/hip_runtime.h>
 
+#include "list_host.h"
 #include "list_voxenc.h"
 #include "mfma_common.h"
 
 namespace {
-
-thread_local char g_voxenc_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_voxenc_err, sizeof(g_voxenc_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
 
 constexpr int kThreads = 256;
 constexpr int kStages = LIST_VOXENC_N_LAYERS - 1;       // 8
@@ -42,8 +30,6 @@ constexpr int kTileHalo = kTile + 2;
 constexpr int kBz = 4, kBy = 4, kBx = 8, kBrick = kBz * kBy * kBx;
 constexpr int kHz = kBz + 2, kHy = kBy + 2, kHx = kBx + 2, kHalo = kHz * kHy * kHx;
 constexpr int kPad = 8;                                 // halfs of padding per LDS row (16 B: rows stay aligned)
-
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
 
 // ---- packed weights and workspace ------------------------------------------------------------------------------------
 // K order of the MFMA convolutions.  C_in >= 32: chunks of 32 input channels, 27 taps per chunk, one MFMA (K = 32) per
@@ -426,15 +412,11 @@ __global__ __launch_bounds__(kThreads) void voxenc_bn_kernel(const float* __rest
 
 unsigned blocks_for(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-int hip_fail(hipError_t e, const char* what) {
-  return fail(LIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" {
 
-const char* list_voxenc_last_error(void) { return g_voxenc_err; }
+const char* list_voxenc_last_error(void) { return g_err; }
 
 size_t list_voxenc_weight_bytes(const int32_t* layers, int32_t n_layers) {
   if (check_layers(layers, n_layers) != LIST_OK) return 0;
@@ -494,8 +476,7 @@ int list_voxenc_prep_weights(const ListVoxencStage* stages, const int32_t* layer
       hipLaunchKernelGGL(voxenc_bn_kernel, dim3(blocks_for(cout)), dim3(kThreads), 0, s, st.bn_weight, st.bn_bias,
                          st.bn_mean, st.bn_var, st.bn_eps, cout, (float*)(base + bn_slot->s),
                          (float*)(base + bn_slot->t));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "list_voxenc_prep_weights");
+    if (int rc = launched("list_voxenc_prep_weights")) return rc;
   }
   return LIST_OK;
 }

@@ -17,7 +17,6 @@ the same computation in numpy -- the CPU fallback and the test oracle:
 import ctypes as C
 import math
 import os
-import threading
 
 import numpy as np
 
@@ -39,27 +38,8 @@ THRESHOLDS = (0.005, 0.01, 0.05)
 # implicit_waterproofing.py:33: the Euler angles of the retries
 EULER_RETRIES = ((0.0, math.pi / 2, 0.0), (math.pi / 2, 0.0, 0.0), (0.0, 0.0, math.pi / 2))
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """The liblist_hip.so of hip.load(), with the symbols of include/list_eval.h bound."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                lib = hip.load()
-                for name, (res, args) in EVAL_EXPORTS.items():
-                    fn = getattr(lib, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = lib
-    return _lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise hip.ListError(what, rc, load().list_eval_last_error().decode("utf-8", "replace"))
+_section = hip.Section(EVAL_EXPORTS, "list_eval_last_error")    # include/list_eval.h on hip.load()'s handle
+load, _check = _section.load, _section.check
 
 
 # ---- counter-based uniforms (list_eval.h) ---------------------------------------------------------------------------
@@ -301,10 +281,7 @@ def sample_surface(verts, faces, n, seed=0):
     v, f = _mesh_tensors(verts, faces)
     lib, dev = load(), v.device
     with torch.cuda.device(dev):
-        need = lib.list_eval_sample_workspace_bytes(f.shape[0])
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_eval_sample_workspace_bytes")
-        ws = hip._workspace(dev, need)
+        ws = _section.workspace(dev, lib.list_eval_sample_workspace_bytes(f.shape[0]), "list_eval_sample_workspace_bytes")
         points = torch.empty((n, 3), dtype=torch.float32, device=dev)
         face_idx = torch.empty((n,), dtype=torch.int32, device=dev)
         _check(lib.list_eval_sample(v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], n, int(seed) & _M64,
@@ -322,10 +299,7 @@ def _contains_flags(v, f, points, hash_res, rot):
     Q = p.shape[0]
     flags = torch.empty((Q,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        need = lib.list_eval_contains_workspace_bytes(f.shape[0], int(hash_res))
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_eval_contains_workspace_bytes")
-        ws = hip._workspace(dev, need)
+        ws = _section.workspace(dev, lib.list_eval_contains_workspace_bytes(f.shape[0], int(hash_res)), "list_eval_contains_workspace_bytes")
         r = None if rot is None else torch.as_tensor(np.asarray(rot, dtype=np.float64).reshape(9), device=dev)
         _check(lib.list_eval_contains(v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], p.data_ptr() if Q else None,
                                       Q, None if r is None else r.data_ptr(), int(hash_res), ws.data_ptr(), ws.numel(),

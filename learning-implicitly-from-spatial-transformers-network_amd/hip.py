@@ -192,9 +192,7 @@ def load():
                     "(hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback for the "
                     "LIST SDF query path.")
             lib = C.CDLL(LIB_PATH)
-            for name, (res, args) in EXPORTS.items():
-                fn = getattr(lib, name)
-                fn.restype, fn.argtypes = res, args
+            _core.bind(lib)
             # the argument structs grow at their end from one ABI version to the next: a library that reads a longer
             # struct than this binding fills would take flags (no_activations, grad_img_map_dtype) from stray bytes
             got = lib.list_abi_version()
@@ -216,9 +214,52 @@ class ListError(RuntimeError):
 ERR_ARG, ERR_SHAPE, ERR_WORKSPACE, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4, -5      # enum ListStatus
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise ListError(what, rc, load().list_last_error().decode("utf-8", "replace"))
+class Section:
+    """One header of the C ABI on load()'s handle: its table of exports (name -> (restype, argtypes)) and the name of
+    its *_last_error symbol.  mesh.py, evaluate.py, prepare.py, chamfer.py, refine.py and voxenc.py hold one each."""
+
+    def __init__(self, exports, last_error_symbol):
+        self.exports, self.last_error_symbol, self._bound = exports, last_error_symbol, None
+
+    def bind(self, lib):
+        for name, (res, args) in self.exports.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        self._bound = lib
+
+    def load(self):
+        """load()'s handle with this section's symbols bound (again, should load() hand out a new handle)."""
+        lib = load()
+        if self._bound is not lib:
+            with _lock:
+                if self._bound is not lib:
+                    self.bind(lib)
+        return lib
+
+    def last_error(self):
+        return getattr(self.load(), self.last_error_symbol)().decode("utf-8", "replace")
+
+    def check(self, rc, what):
+        if rc != 0:
+            raise ListError(what, rc, self.last_error())
+
+    def sized(self, need, sized_by):
+        """`need` as the *_bytes query `sized_by` returned it; 0 is that query's refusal, whose text it has set."""
+        if need == 0:
+            self.check(ERR_SHAPE, sized_by)
+        return need
+
+    def workspace(self, device, need, sized_by):
+        """The calling thread's cached workspace (_workspace) of `need` bytes, sized by the query `sized_by`."""
+        return _workspace(device, self.sized(need, sized_by))
+
+
+_core = Section(EXPORTS, "list_last_error")
+_check, _last_error = _core.check, _core.last_error
+
+
+def _precision(p):
+    return PRECISIONS[p] if isinstance(p, str) else int(p)
 
 
 def _stream():
@@ -262,21 +303,32 @@ class PackedMlp:
         self.vox_C, self.img_C, self.fp16 = list(vox_C), img_C, fp16
 
 
+def _map2d_descriptors(levels):
+    """The ListMap2D descriptors of the five [B,C,H,W] tensors of an encoder pyramid (or of its gradient)."""
+    maps = (ListMap2D * N_IMG_LEVELS)()
+    for i, t in enumerate(levels):
+        maps[i] = ListMap2D(t.data_ptr(), t.shape[1], t.shape[2], t.shape[3], *t.stride())
+    return maps
+
+
+def _encoder_maps(img_featuremaps):
+    """The encoder's five float32 device maps, validated -> (descriptors, B, channels of each level)."""
+    B = img_featuremaps[0].shape[0]
+    for i, t in enumerate(img_featuremaps):
+        _f32_cuda(t, f"img_featuremaps[{i}]")
+        if t.dim() != 4 or t.shape[0] != B:
+            raise RuntimeError(f"img_featuremaps[{i}] must be [B,C,H,W]")
+    return _map2d_descriptors(img_featuremaps), B, [t.shape[1] for t in img_featuremaps]
+
+
 def prep_img_maps(img_featuremaps, map_size=137, dtype="f32"):
     """F.interpolate x5 (+ layout) of the reference, network/modules.py:26-35."""
     lib = load()
     md = MAP_DTYPES[dtype]
     if len(img_featuremaps) != N_IMG_LEVELS:
         raise RuntimeError(f"expected {N_IMG_LEVELS} image feature maps, got {len(img_featuremaps)}")
-    maps = (ListMap2D * N_IMG_LEVELS)()
-    B = img_featuremaps[0].shape[0]
-    Ct = 0
-    for i, t in enumerate(img_featuremaps):
-        _f32_cuda(t, f"img_featuremaps[{i}]")
-        if t.dim() != 4 or t.shape[0] != B:
-            raise RuntimeError(f"img_featuremaps[{i}] must be [B,C,H,W]")
-        maps[i] = ListMap2D(t.data_ptr(), t.shape[1], t.shape[2], t.shape[3], *t.stride())
-        Ct += t.shape[1]
+    maps, B, channels = _encoder_maps(img_featuremaps)
+    Ct = sum(channels)
     out = torch.empty((B, map_size, map_size, Ct), dtype=torch.float16 if md == MAP_F16 else torch.float32,
                       device=img_featuremaps[0].device)
     with torch.cuda.device(out.device):
@@ -310,29 +362,21 @@ def prep_img_proj(img_featuremaps, packed, map_size=137, precision="bf16x3", n_k
     through their columns of fc_0 before the resize (F.interpolate and fc_0 are both linear and commute:
     network/modules.py:26-35, 276).  -> PreparedImage for sdf_query(..., save_for_backward=False) with `packed`."""
     lib = load()
-    prec = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    prec = _precision(precision)
     if len(img_featuremaps) != N_IMG_LEVELS:
         raise RuntimeError(f"expected {N_IMG_LEVELS} image feature maps, got {len(img_featuremaps)}")
     if n_kept_levels is None:
         n_kept_levels = img_proj_kept_levels(img_featuremaps, map_size)
     if not 0 <= n_kept_levels < N_IMG_LEVELS:
         raise ListError("prep_img_proj", ERR_UNSUPPORTED, "no encoder level is small enough to project")
-    maps = (ListMap2D * N_IMG_LEVELS)()
-    B = img_featuremaps[0].shape[0]
-    Ct = kept = 0
-    for i, t in enumerate(img_featuremaps):
-        _f32_cuda(t, f"img_featuremaps[{i}]")
-        if t.dim() != 4 or t.shape[0] != B:
-            raise RuntimeError(f"img_featuremaps[{i}] must be [B,C,H,W]")
-        maps[i] = ListMap2D(t.data_ptr(), t.shape[1], t.shape[2], t.shape[3], *t.stride())
-        Ct += t.shape[1]
-        kept += t.shape[1] if i < n_kept_levels else 0
+    maps, B, channels = _encoder_maps(img_featuremaps)
+    Ct, kept = sum(channels), sum(channels[:n_kept_levels])
     if Ct != packed.img_C:
         raise RuntimeError(f"the encoder levels hold {Ct} channels, the packed weights expect {packed.img_C}")
     nbytes = lib.list_img_proj_map_bytes(maps, B, map_size, n_kept_levels, packed.H1, prec)
     sbytes = lib.list_img_proj_scratch_bytes(maps, B, n_kept_levels, packed.H1, prec)
     if nbytes == 0 or sbytes == 0:
-        raise ListError("list_img_proj_map_bytes", ERR_UNSUPPORTED, lib.list_last_error().decode("utf-8", "replace"))
+        raise ListError("list_img_proj_map_bytes", ERR_UNSUPPORTED, _last_error())
     dev = img_featuremaps[0].device
     f16 = prec == PREC_FP16
     out = torch.empty((B, map_size, map_size, kept + packed.H1), dtype=torch.float16 if f16 else torch.float32, device=dev)
@@ -390,43 +434,36 @@ def _mlp_weights_struct(params, vox_C, img_C, precision):
     for i, c in enumerate(vox_C):
         w.vox_C[i] = int(c)
     w.img_C = int(img_C)
-    w.precision = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    w.precision = _precision(precision)
     return w, ts
+
+
+def _pack_mlp(params, vox_C, img_C, precision, bytes_fn, prep_fn):
+    """The weights through one of the library's two packers -> (packed bytes on the weights' device, ListMlpWeights)."""
+    lib = load()
+    w, ts = _mlp_weights_struct(params, vox_C, img_C, precision)
+    need = getattr(lib, bytes_fn)(C.byref(w))
+    if need == 0:
+        raise RuntimeError(f"{bytes_fn} failed: " + _last_error())
+    dev = ts["fc_0"][0].device
+    packed = torch.empty((need,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(getattr(lib, prep_fn)(C.byref(w), packed.data_ptr(), need, _stream()), prep_fn)
+    # temporaries made by .contiguous() are released stream-ordered by the caching allocator, and
+    # every kernel above was enqueued on the same (current) stream: no synchronisation needed
+    return packed, w
 
 
 def prep_mlp_weights(params, vox_C, img_C=1024, precision="bf16x3"):
     """params: dict with fc_0/fc_1/fc_2/fc_out .weight/.bias (reference state_dict names,
     network/modules.py:196-200).  Conv1d weights may be [out,in,1] or [out,in]."""
-    lib = load()
-    w, ts = _mlp_weights_struct(params, vox_C, img_C, precision)
-    need = lib.list_packed_mlp_bytes(C.byref(w))
-    if need == 0:
-        raise RuntimeError("list_packed_mlp_bytes failed: "
-                           + lib.list_last_error().decode("utf-8", "replace"))
-    dev = ts["fc_0"][0].device
-    packed = torch.empty((need,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.list_prep_mlp_weights(C.byref(w), packed.data_ptr(), need, _stream()),
-               "list_prep_mlp_weights")
-    # temporaries made by .contiguous() are released stream-ordered by the caching allocator, and
-    # every kernel above was enqueued on the same (current) stream: no synchronisation needed
+    packed, w = _pack_mlp(params, vox_C, img_C, precision, "list_packed_mlp_bytes", "list_prep_mlp_weights")
     return PackedMlp(packed, w.F, w.H1, w.H2, w.H3, vox_C, img_C, w.precision == PREC_FP16)
 
 
 def prep_mlp_weights_bwd(params, vox_C, img_C=1024, precision="bf16x3"):
     """Transposed 16-bit copies of fc_0..fc_2 for the data-gradient GEMMs of list_sdf_query_bwd."""
-    lib = load()
-    w, ts = _mlp_weights_struct(params, vox_C, img_C, precision)
-    need = lib.list_packed_mlp_bwd_bytes(C.byref(w))
-    if need == 0:
-        raise RuntimeError("list_packed_mlp_bwd_bytes failed: "
-                           + lib.list_last_error().decode("utf-8", "replace"))
-    dev = ts["fc_0"][0].device
-    packed = torch.empty((need,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.list_prep_mlp_weights_bwd(C.byref(w), packed.data_ptr(), need, _stream()),
-               "list_prep_mlp_weights_bwd")
-    return packed
+    return _pack_mlp(params, vox_C, img_C, precision, "list_packed_mlp_bwd_bytes", "list_prep_mlp_weights_bwd")[0]
 
 
 class PercepProj:
@@ -442,7 +479,7 @@ def prep_percep_proj(img, packed, precision="bf16x3"):
     to a bilinear sample of the prepared map equals the bilinear sample of the projected map.  -> PercepProj for
     sdf_query(..., percep_proj=...).  Raises RuntimeError(unsupported) for shapes / dtype pairs the path does not take."""
     lib = load()
-    prec = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    prec = _precision(precision)
     B = img.data.shape[0]
     nbytes = lib.list_percep_proj_bytes(B, img.map_size, packed.H1, prec)
     sbytes = lib.list_percep_proj_scratch_bytes(B, img.map_size, img.channels, prec)
@@ -523,7 +560,7 @@ def _fill_query_args(query, perm, scale, vox, packed, precision, trans_mat=None,
         a.vox[i] = vox.levels[i]
     a.packed_mlp = packed.data.data_ptr()
     a.F, a.H1, a.H2, a.H3 = packed.F, packed.H1, packed.H2, packed.H3
-    a.precision = PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    a.precision = _precision(precision)
     if (a.precision == PREC_FP16) != bool(packed.fp16):
         raise RuntimeError("packed MLP weights were prepared for a different precision "
                            "(fp16 vs bf16 planes); call prep_mlp_weights(..., precision=...) again")
@@ -744,15 +781,10 @@ def _level_descriptors(like, img_C):
     """Fresh gradients shaped and strided like the encoder's maps + their ListMap2D descriptors."""
     if len(like) != N_IMG_LEVELS:
         raise RuntimeError(f"need {N_IMG_LEVELS} image levels, got {len(like)}")
-    maps = (ListMap2D * N_IMG_LEVELS)()
-    outs = []
-    for i, t in enumerate(like):
-        o = torch.empty_like(t, dtype=torch.float32)
-        outs.append(o)
-        maps[i] = ListMap2D(o.data_ptr(), o.shape[1], o.shape[2], o.shape[3], *o.stride())
+    outs = [torch.empty_like(t, dtype=torch.float32) for t in like]
     if sum(o.shape[1] for o in outs) != img_C:
         raise RuntimeError("channel counts of `like` do not add up to the prepared map's")
-    return maps, outs
+    return _map2d_descriptors(outs), outs
 
 
 def img_map_grad_to_levels(grad_img_map, like):
@@ -801,13 +833,11 @@ def gather_features(query, trans_mat, img, vox, packed, perm=(2, 1, 0), scale=2.
     return out
 
 
-def percep_pool(pc, trans_mat, img, clamp_hi=136.0):
-    """PerceptualPooling.forward on a prepared map -> [B,Ct,1,N] (network/modules.py:37-53)."""
-    lib = load()
+def _pool_args(pc, trans_mat, img, clamp_hi):
+    """ListPoolArgs of a pooling call, `out` left unset -> (args, the [B,4,3] matrices they point into)."""
     _f32_cuda(pc, "pc")
     B, N, _ = pc.shape
     tm = _f32_cuda(trans_mat, "trans_mat").reshape(B, 4, 3).contiguous()
-    out = torch.empty((B, img.channels, 1, N), dtype=torch.float32, device=pc.device)
     a = ListPoolArgs()
     a.B, a.N = B, N
     a.pc = pc.data_ptr()
@@ -816,6 +846,14 @@ def percep_pool(pc, trans_mat, img, clamp_hi=136.0):
     a.img_map, a.map_size, a.img_C = img.data.data_ptr(), img.map_size, img.channels
     a.img_dtype = img.dtype
     a.clamp_hi = float(clamp_hi)
+    return a, tm
+
+
+def percep_pool(pc, trans_mat, img, clamp_hi=136.0):
+    """PerceptualPooling.forward on a prepared map -> [B,Ct,1,N] (network/modules.py:37-53)."""
+    lib = load()
+    a, tm = _pool_args(pc, trans_mat, img, clamp_hi)
+    out = torch.empty((a.B, img.channels, 1, a.N), dtype=torch.float32, device=pc.device)
     a.out = out.data_ptr()
     with torch.cuda.device(pc.device):
         _check(lib.list_percep_pool_fwd(C.byref(a), _stream()), "list_percep_pool_fwd")
@@ -826,18 +864,9 @@ def percep_pool_backward(pc, trans_mat, img, grad_out, want_img=True, want_trans
     """Backward of percep_pool (list_percep_pool_bwd): grad_out [B,Ct,1,N] or [B,Ct,N] ->
     {'img_map': [B,ms,ms,Ct] fp32, 'trans_mat': [B,4,3]}."""
     lib = load()
-    _f32_cuda(pc, "pc")
-    B, N, _ = pc.shape
-    tm = _f32_cuda(trans_mat, "trans_mat").reshape(B, 4, 3).contiguous()
+    fwd, tm = _pool_args(pc, trans_mat, img, clamp_hi)
+    B, N = fwd.B, fwd.N
     g = _f32_cuda(grad_out, "grad_out").reshape(B, img.channels, N)
-    fwd = ListPoolArgs()
-    fwd.B, fwd.N = B, N
-    fwd.pc = pc.data_ptr()
-    fwd.p_sb, fwd.p_sn, fwd.p_sc = pc.stride()
-    fwd.trans_mat = tm.data_ptr()
-    fwd.img_map, fwd.map_size, fwd.img_C = img.data.data_ptr(), img.map_size, img.channels
-    fwd.img_dtype = img.dtype
-    fwd.clamp_hi = float(clamp_hi)
     ga = ListPoolGradArgs()
     ga.fwd = C.pointer(fwd)
     ga.grad_out = g.data_ptr()

@@ -15,7 +15,6 @@ fallback and the test oracle.  Both give, in the same order:
 import ctypes as C
 import os
 import re
-import threading
 
 import numpy as np
 
@@ -34,27 +33,8 @@ MESH_EXPORTS = {
     "list_mesh_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """The liblist_hip.so of hip.load(), with the symbols of include/list_mesh.h bound."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                lib = hip.load()
-                for name, (res, args) in MESH_EXPORTS.items():
-                    fn = getattr(lib, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = lib
-    return _lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise hip.ListError(what, rc, load().list_mesh_last_error().decode("utf-8", "replace"))
+_section = hip.Section(MESH_EXPORTS, "list_mesh_last_error")    # include/list_mesh.h on hip.load()'s handle
+load, _check = _section.load, _section.check
 
 
 # ---- tables ---------------------------------------------------------------------------------------------------------
@@ -108,9 +88,7 @@ def marching_cubes(volume, level=0.0, bb_min=-0.5, bb_max=0.5):
     the volume's device, computed on its current stream.  The one host synchronisation reads V and F back.
     bb_min / bb_max: scalars or one value per axis."""
     import torch
-    if not isinstance(volume, torch.Tensor) or volume.dtype != torch.float32 or not volume.is_cuda:
-        raise RuntimeError(f"volume must be a float32 CUDA/HIP tensor (got {type(volume).__name__} "
-                           f"{getattr(volume, 'dtype', None)} {getattr(volume, 'device', None)})")
+    hip._f32_cuda(volume, "volume")
     _check_shape(volume.shape)
     bmin, bmax = _bounds3(bb_min, "bb_min"), _bounds3(bb_max, "bb_max")
     lib = load()
@@ -118,10 +96,7 @@ def marching_cubes(volume, level=0.0, bb_min=-0.5, bb_max=0.5):
     X, Y, Z = (int(s) for s in volume.shape)
     with torch.cuda.device(dev):
         vol = volume.contiguous()
-        need = lib.list_mc_workspace_bytes(X, Y, Z)
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_mc_workspace_bytes")
-        ws = hip._workspace(dev, need)
+        ws = _section.workspace(dev, lib.list_mc_workspace_bytes(X, Y, Z), "list_mc_workspace_bytes")
         totals = torch.empty((2,), dtype=torch.int64, device=dev)
         stream = hip._stream()
         _check(lib.list_mc_count(vol.data_ptr(), X, Y, Z, float(level), ws.data_ptr(), ws.numel(), totals.data_ptr(),

@@ -18,7 +18,6 @@ import ctypes as C
 import math
 import os
 import sys
-import threading
 import traceback
 from glob import glob
 
@@ -40,27 +39,8 @@ MAX_FPS_POINTS = 65536                                    # LIST_DATA_MAX_FPS_PO
 SIGMAS = (0.003, 0.01, 0.07)                              # preprocess.py's --sigma default
 _BOUNDARY_BASE = 1 << 63                                  # boundary_samples' counters: 2^63 + 6 i + 2 k (+1)
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """The liblist_hip.so of hip.load(), with the symbols of include/list_data.h bound."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                lib = hip.load()
-                for name, (res, args) in DATA_EXPORTS.items():
-                    fn = getattr(lib, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = lib
-    return _lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise hip.ListError(what, rc, load().list_data_last_error().decode("utf-8", "replace"))
+_section = hip.Section(DATA_EXPORTS, "list_data_last_error")    # include/list_data.h on hip.load()'s handle
+load, _check = _section.load, _section.check
 
 
 def _host(a, dtype):
@@ -95,10 +75,7 @@ def signed_distance(verts, faces, points, with_winding=False):
     face_idx = torch.empty((Q,), dtype=torch.int32, device=dev)
     winding = torch.empty((Q,), dtype=torch.float32, device=dev) if with_winding else None
     with torch.cuda.device(dev):
-        need = lib.list_data_signed_distance_workspace_bytes(f.shape[0])
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_data_signed_distance_workspace_bytes")
-        ws = hip._workspace(dev, need)
+        ws = _section.workspace(dev, lib.list_data_signed_distance_workspace_bytes(f.shape[0]), "list_data_signed_distance_workspace_bytes")
         _check(lib.list_data_signed_distance(
             v.data_ptr() if v.numel() else None, v.shape[0], f.data_ptr(), f.shape[0], p.data_ptr() if Q else None, Q,
             ws.data_ptr(), ws.numel(), sdf.data_ptr() if Q else None, face_idx.data_ptr() if Q else None,

@@ -23,7 +23,6 @@ The steps run on the device through liblist_hip.so (include/list_refine.h); clas
 fill_cpu restate them in numpy, bit for bit: the test oracle and the CPU path of predict_grid_refined.
 """
 import ctypes as C
-import threading
 
 import numpy as np
 
@@ -44,27 +43,8 @@ REFINE_EXPORTS = {
     "list_refine_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """The liblist_hip.so of hip.load(), with the symbols of include/list_refine.h bound."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                lib = hip.load()
-                for name, (res, args) in REFINE_EXPORTS.items():
-                    fn = getattr(lib, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = lib
-    return _lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise hip.ListError(what, rc, load().list_refine_last_error().decode("utf-8", "replace"))
+_section = hip.Section(REFINE_EXPORTS, "list_refine_last_error")    # include/list_refine.h on hip.load()'s handle
+load, _check = _section.load, _section.check
 
 
 # ---- geometry -------------------------------------------------------------------------------------------------------
@@ -231,9 +211,7 @@ def count(lattice, R, s, level=0.0, band=None):
     lib = load()
     dev = lattice.device
     with torch.cuda.device(dev):
-        need = lib.list_refine_workspace_bytes(R, s)
-        if need == 0:
-            _check(hip.ERR_SHAPE, "list_refine_workspace_bytes")
+        need = _section.sized(lib.list_refine_workspace_bytes(R, s), "list_refine_workspace_bytes")
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
         total = torch.empty((1,), dtype=torch.int64, device=dev)
         lat = lattice.contiguous()

@@ -13,7 +13,6 @@ saturated.  Eval mode only: the training forward (batch-statistics BN) and the b
   encode_cpu(occ, params, storage)   the numpy restatement: the test oracle, not a path of the model
 """
 import ctypes as C
-import threading
 
 import numpy as np
 
@@ -43,31 +42,8 @@ VOXENC_EXPORTS = {
     "list_voxenc_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """The liblist_hip.so of hip.load(), with the symbols of include/list_voxenc.h bound."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                lib = hip.load()
-                for name, (res, args) in VOXENC_EXPORTS.items():
-                    fn = getattr(lib, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = lib
-    return _lib
-
-
-def last_error():
-    return load().list_voxenc_last_error().decode("utf-8", "replace")
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise hip.ListError(what, rc, last_error())
+_section = hip.Section(VOXENC_EXPORTS, "list_voxenc_last_error")    # include/list_voxenc.h on hip.load()'s handle
+load, _check, last_error = _section.load, _section.check, _section.last_error
 
 
 def _layers_arg(layers):
@@ -112,18 +88,12 @@ def workspace_bytes_closed_form(B, R, layers):
 
 def weight_bytes(layers):
     arr, n = _layers_arg(layers)
-    need = load().list_voxenc_weight_bytes(arr, n)
-    if need == 0:
-        _check(hip.ERR_SHAPE, "list_voxenc_weight_bytes")
-    return need
+    return _section.sized(load().list_voxenc_weight_bytes(arr, n), "list_voxenc_weight_bytes")
 
 
 def workspace_bytes(B, R, layers):
     arr, n = _layers_arg(layers)
-    need = load().list_voxenc_workspace_bytes(int(B), int(R), arr, n)
-    if need == 0:
-        _check(hip.ERR_SHAPE, "list_voxenc_workspace_bytes")
-    return need
+    return _section.sized(load().list_voxenc_workspace_bytes(int(B), int(R), arr, n), "list_voxenc_workspace_bytes")
 
 
 # ---- parameters ------------------------------------------------------------------------------------------------------

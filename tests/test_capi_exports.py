@@ -1,36 +1,45 @@
-"""CPU: the C-ABI library loads and exports every symbol include/list_hip.h declares
-(no compute call is made here: there is no GPU in the authoring container)."""
+"""CPU: the C-ABI library loads and exports every symbol its seven headers declare, and each binding's table lists
+exactly those (no compute call is made here: there is no GPU in the authoring container)."""
 import ctypes
 import os
-import re
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _capi_headers as H  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "list_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(list_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_header_declares_expected_entry_points():
-    names = _declared()
+    names = H.declared("list_hip.h")
     for must in ("list_sdf_query_fwd", "list_prep_img_maps", "list_prep_vox_maps",
                  "list_prep_mlp_weights", "list_percep_pool_fwd", "list_query_workspace_bytes",
                  "list_last_error"):
         assert must in names
 
 
-def test_library_exports_every_declared_symbol():
+@pytest.mark.parametrize("header", list(H.SECTIONS))
+def test_header_table_and_library_agree(header):
+    """What a header declares == what its binding's table lists == what the library exports under its prefixes."""
+    import importlib
     import __graft_entry__ as ge
     ge.build()
     from list_amd import hip
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in _declared():
-        assert hasattr(lib, name), f"{name} declared in list_hip.h but not exported"
-    assert set(hip.EXPORTS) == set(_declared())
+    module, table, prefixes = H.SECTIONS[header]
+    module = importlib.import_module("list_amd." + module)
+    names, exported = H.declared(header), H.exported(hip.LIB_PATH)
+    assert names == sorted(getattr(module, table))
+    raw, lib = ctypes.CDLL(hip.LIB_PATH), module.load()
+    for name in names:
+        assert hasattr(raw, name), f"{name} declared in {header} but not exported"
+        assert getattr(lib, name) is not None
+    assert set(names) <= exported
+    assert hip.ABI_VERSION == 9 and lib.list_abi_version() == 9
+    if prefixes:      # a section owns its prefixes: nothing undeclared is exported under them, list_hip.h's table is untouched
+        assert {n for n in exported if n.startswith(prefixes)} == set(names)
+        assert not set(names) & set(hip.EXPORTS) and not any(n.startswith(prefixes) for n in hip.EXPORTS)
 
 
 def test_abi_version_and_error_string_without_gpu():
@@ -96,3 +105,14 @@ def test_binding_refuses_a_library_of_another_abi_version(monkeypatch):
         hip.load()
     assert hip._lib is None                          # nothing half-loaded is left behind
 
+
+def test_each_section_keeps_its_own_error_text():
+    """The sections share their host plumbing as source, not as state: a refused Chamfer call leaves
+    list_mesh_last_error() and list_last_error() as they were."""
+    from list_amd import chamfer, hip, mesh
+    lib = hip.load()
+    assert mesh.load().list_mc_workspace_bytes(1, 1, 1) == 0 and lib.list_sdf_query_fwd(None, None) == hip.ERR_ARG
+    before = lib.list_mesh_last_error(), lib.list_last_error()
+    assert b"axis" in before[0] and b"NULL" in before[1]
+    assert chamfer.load().list_chamfer_workspace_bytes(0, 5, 5) == 0 and b"B = 0" in lib.list_loss_last_error()
+    assert (lib.list_mesh_last_error(), lib.list_last_error()) == before

