@@ -238,7 +238,11 @@ typedef struct ListQueryArgs {
                                         /*   into LDS inside the kernel, no 2-D gather kernel is launched    */
                                         /*   and those columns of the feature matrix never reach HBM.  1:    */
                                         /*   the unfused pair (k_gather_img + k_gemm_nt_pp).  Same bits      */
-                                        /*   either way (tests/test_fused_fc0_gpu.py).                       */
+                                        /*   either way (tests/test_fused_fc0_gpu.py).  With img_proj (fp16) */
+                                        /*   0 means: k_gather_img samples the kept channels only and        */
+                                        /*   k_gemm_nt_pp's epilogue samples the projected ones from the map */
+                                        /*   (no row-vector buffer); 1: k_gather_img writes row vectors.     */
+                                        /*   Same bits (tests/test_fc0_sampled_epilogue_gpu.py).             */
   int32_t img_proj;                     /* ABI 8.  1: img_map is the output of list_prep_img_proj for packed_mlp: */
   int32_t img_kept_C;                   /*   img_kept_C sampled channels followed by H1 projected ones per pixel  */
                                         /*   (img_C stays the channel count of the feature layout, 1024).         */
@@ -292,8 +296,11 @@ typedef struct ListQueryPlan {
                             /*    args->percep_proj is given)                                                      */
   int32_t box_levels;       /* bit l: voxel level l is gathered on the matrix cores (k_gather_vox_box: a level whose  */
                             /*    stencil stays inside one cell, 128 channels, fp16 maps and fp16 operands)           */
-  int32_t fused_fc0;        /* 1: fc_0 produces the perceptual block of its A operand on chip (k_fc0_fused) and no 2-D   */
-                            /*    gather kernel is launched; 0: k_gather_img writes the block into X                     */
+  int32_t fused_fc0;        /* 1: fc_0 samples the perceptual map itself; no row-vector buffer, no pixel order in the    */
+                            /*    sort: k_fc0_fused produces the perceptual block of its A operand on chip (no 2-D gather */
+                            /*    launch), or, with img_proj in fp16, k_gemm_nt_pp samples the projected channels in its  */
+                            /*    epilogue behind a 2-D gather of the kept channels alone.  0: k_gather_img writes the    */
+                            /*    block (and the row vectors of img_proj) for fc_0 to read                                */
   int32_t img_proj;         /* 1: the projected levels' columns are left out of fc_0's K loop (ListQueryArgs.img_proj)      */
 } ListQueryPlan;
 int list_query_plan(const ListQueryArgs* args, ListQueryPlan* plan);

@@ -33,22 +33,10 @@ constexpr int kFAOff = 2 * kFW;                     // A stages behind the two W
 
 __device__ __forceinline__ int fswz(int row) { return (row >> 1) & 7; }
 
-// per-thread record of one row's projection (project(), point_math.h), packed: what the four tap loads need
-// (valid: bit 0 = the row is a query point, bits 1..4 = Proj::dead, the taps outside the map)
-struct RowProj { int64_t base; int dx, dy; float w00, w01, w10, w11; int valid; };
-// the same per ROW of the tile, in LDS for the epilogue of the PROJ variant (48 B: three 16-B reads)
-struct RowProjRec { int64_t base; int dx, dy; float w00, w01, w10, w11; int valid, pad_[3]; };
-constexpr int kFProjRecOff = 81920;                 // behind the epilogue's staging tiles (8 waves x 32 x kStageLd floats)
-
-// PROJ (fp16 operands; list_prep_img_proj, ListQueryArgs.img_proj): the map holds fp.kept sampled channels followed by
-// N = 512 PROJECTED channels per pixel -- the low-resolution encoder levels already multiplied by their columns of
-// fc_0.  K-tiles 0 .. kept/64 - 1 are produced on chip as before, the projected levels' K-tiles do not exist (gp.k_gap),
-// and the epilogue adds the bilinear sample of the projected channels to the accumulators before bias and ReLU: in the
-// staged layout a thread owns (row, 8 consecutive columns) = (point, 8 consecutive projected channels), one 16-B load
-// per tap.  No 2-D gather kernel, no row-vector buffer.
-template <int X3, bool PROJ = false>
+// (Forwards with list_prep_img_proj's map, whose perceptual block is 2 K-tiles of 43, do not come here: they take the
+// 256 x 256 ping-pong kernel with the sampling epilogue, gemm_kernels.hip EPI_RELU_SAMPLE.)
+template <int X3>
 __global__ __launch_bounds__(512, 2) void k_fc0_fused(FusedFc0Params fp) {
-  static_assert(!PROJ || X3 == 0, "the projected form is built for fp16 operands");
   constexpr bool F16 = X3 == 0;
   constexpr int KT = F16 ? 64 : 32;                 // feature columns per K-tile (128 operand bytes per row)
   using M = MapT<F16 ? 1 : 0>;
@@ -63,22 +51,16 @@ __global__ __launch_bounds__(512, 2) void k_fc0_fused(FusedFc0Params fp) {
   const int nk = p.K / KT;
   const int np = fp.n_produced;
   const int64_t lda = (int64_t)(p.lda ? p.lda : p.K) * (F16 ? 2 : 4), ldw = lda;      // bytes per operand row (hi + lo interleaved)
-  // byte offset of K-tile t in the operand rows (tiles from k_gap_at on lie k_gap tiles further: gemm_kernels.hip)
-  const int gap_at = p.k_gap_at, gap = p.k_gap;
-  auto ktb = [&](int t) { return (t + (t >= gap_at ? gap : 0)) * 128; };
+  auto ktb = [&](int t) { return t * 128; };          // byte offset of K-tile t in the operand rows
 
   // ---- the two items of this thread in a produced K-tile: rows r0, r0 + 64, chunk c (16 B of map: 8 halfs / 4 floats)
   const int pc = tid & 7, pr = tid >> 3;
-  RowProj rp[2];
-  if (np > 0 || PROJ) {
+  RowProjRec rp[2];
+  if (np > 0) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const Pt pt = load_point(fp.g, m0 + pr + 64 * h);
-      const Proj q = project(fp.trans_mat + pt.b * 12, pt.x, pt.y, pt.z, fp.ms, fp.Ct, fp.clamp_hi);
-      rp[h].base = (int64_t)pt.b * fp.ms * fp.ms * fp.Ct + q.o00 + pc * M::V;
-      rp[h].dx = q.o01 - q.o00; rp[h].dy = q.o10 - q.o00;        // (o11 = o00 + dx + dy: x1, y1 are clamped separately)
-      rp[h].w00 = q.w00; rp[h].w01 = q.w01; rp[h].w10 = q.w10; rp[h].w11 = q.w11;
-      rp[h].valid = (pt.valid ? 1 : 0) | (q.dead << 1);
+      rp[h] = row_proj_rec(fp.g, fp.trans_mat, fp.ms, fp.Ct, fp.clamp_hi, m0 + pr + 64 * h);
+      rp[h].base += pc * M::V;
     }
   }
   typename M::Raw taps[2][4];
@@ -239,41 +221,10 @@ __global__ __launch_bounds__(512, 2) void k_fc0_fused(FusedFc0Params fp) {
     const int col_base = wn * 128;
     bool bad = false;
     __syncthreads();                                 // every wave is done with the operand stages
-    const RowProjRec* recs = (const RowProjRec*)(smem + kFProjRecOff);
-    if constexpr (PROJ) {
-      // the projections of the tile's 128 rows, from the threads that hold them (chunk 0 of rows pr and pr + 64)
-      if (pc == 0) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          RowProjRec rc;
-          rc.base = rp[h].base; rc.dx = rp[h].dx; rc.dy = rp[h].dy;
-          rc.w00 = rp[h].w00; rc.w01 = rp[h].w01; rc.w10 = rp[h].w10; rc.w11 = rp[h].w11; rc.valid = rp[h].valid;
-          rc.pad_[0] = rc.pad_[1] = rc.pad_[2] = 0;
-          *(RowProjRec*)(smem + kFProjRecOff + (pr + 64 * h) * (int)sizeof(RowProjRec)) = rc;
-        }
-      }
-      __syncthreads();
-    }
 #pragma unroll
     for (int ih = 0; ih < 2; ++ih)
 #pragma unroll
       for (int jh = 0; jh < 2; ++jh) {
-        // PROJ: the four taps of this turn's four (row, 8 projected channels) items, requested before the staging.
-        // (Round 4b, one box, two interleaved pairs: the sampling costs 0.07 ms of the kernel's 0.545 -- without the
-        // loads 0.474 --; requesting turn t + 1's taps behind turn t's staging stores, two tap buffers, made it SLOWER,
-        // 0.545 -> 0.563 ms with 108 instead of 68 B of scratch: not round-trip latency, the bytes themselves.)
-        [[maybe_unused]] uint4 ptap[4][4];
-        if constexpr (PROJ) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const RowProjRec& rc = recs[wm * 64 + ih * 32 + rr + 8 * k];
-            const int64_t o = rc.base + fp.kept + col_base + jh * 64 + c8;
-            ptap[k][0] = M::load(fp.img_map, o);
-            ptap[k][1] = M::load(fp.img_map, o + rc.dx);
-            ptap[k][2] = M::load(fp.img_map, o + rc.dy);
-            ptap[k][3] = M::load(fp.img_map, o + rc.dy + rc.dx);
-          }
-        }
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
@@ -292,30 +243,8 @@ __global__ __launch_bounds__(512, 2) void k_fc0_fused(FusedFc0Params fp) {
           const float4 y = *(const float4*)(tile + r * kStageLd + c8 + 4);
           const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
           float o[8];
-          if constexpr (PROJ) {
-            // the projected sample of (row, 8 channels): out-of-map taps masked like the reference (k_gather_img's
-            // OUT32 form, reduce_proj_exact), rows beyond the query contribute nothing; (acc + sample) + bias, the K sum
-            // first, as k_gemm_nt_pp's row-vector epilogue adds it
-            const RowProjRec& rc = recs[wm * 64 + ih * 32 + r];
-            const float wt[4] = {rc.w00, rc.w01, rc.w10, rc.w11};
-            float sm[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) sm[e] = 0.f;
-#pragma unroll
-            for (int tp = 0; tp < 4; ++tp) {
-              float f[8];
-              M::unpack(ptap[k][tp], f);
-              const bool dead = (rc.valid >> (1 + tp)) & 1;
-#pragma unroll
-              for (int e = 0; e < 8; ++e) sm[e] = fmaf(dead ? 0.f : f[e], wt[tp], sm[e]);
-            }
-            const bool live = (rc.valid & 1) != 0;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { o[e] = relu_nan((v[e] + (live ? sm[e] : 0.f)) + bb[e]); bad = bad || (o[e] != o[e]); }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { o[e] = relu_nan(v[e] + bb[e]); bad = bad || (o[e] != o[e]); }
-          }
+          for (int e = 0; e < 8; ++e) { o[e] = relu_nan(v[e] + bb[e]); bad = bad || (o[e] != o[e]); }
           store8_planes<F16 ? 1 : 0>(p.out_hi, F16 ? nullptr : p.out_lo, (row_base + ih * 32 + r) * p.ldo + cb, o);
         }
         __syncthreads();
@@ -326,10 +255,10 @@ __global__ __launch_bounds__(512, 2) void k_fc0_fused(FusedFc0Params fp) {
 }
 
 bool fused_fc0_eligible(const GemmParams& gp, int img_f16, int img_C) {
-  // (img_C: the channels produced on chip -- all of the perceptual block, or the kept levels of list_prep_img_proj)
+  // (img_C: the channels produced on chip -- all of the perceptual block)
   if (gp.N != 512 || gp.M <= 0 || gp.M % 128 || gp.K % 64 || img_C < 0 || img_C % 64 || img_C > gp.K || !gp.bias ||
-      gp.rowvec || gp.a_rows || gp.tile_gate) return false;
-  if (gp.lda != gp.ldw || (gp.k_gap && !gp.lda)) return false;
+      gp.rowvec || gp.a_rows || gp.tile_gate || gp.k_gap) return false;
+  if (gp.lda != gp.ldw) return false;
   // fp16 operands pair with fp16 maps; the bf16 formats (interleaved hi / lo operands) with fp32 maps
   return gp.fmt == FMT_FP16 ? (img_f16 != 0 && !gp.x3i) : (img_f16 == 0 && gp.x3i != 0);
 }
@@ -337,12 +266,9 @@ bool fused_fc0_eligible(const GemmParams& gp, int img_f16, int img_C) {
 // terms: 3 = bf16x3, 1 = plain bf16 (split formats only)
 hipError_t launch_fc0_fused(const FusedFc0Params& fp, int terms, hipStream_t s) {
   const dim3 grid(fp.gp.M / 128);
-  if (fp.proj) {
-    if (fp.gp.fmt != FMT_FP16 || fp.gp.N != 512) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_fc0_fused<0, true>), grid, dim3(512), 0, s, fp);
-  } else if (fp.gp.fmt == FMT_FP16) hipLaunchKernelGGL((k_fc0_fused<0, false>), grid, dim3(512), 0, s, fp);
-  else if (terms == 3) hipLaunchKernelGGL((k_fc0_fused<3, false>), grid, dim3(512), 0, s, fp);
-  else hipLaunchKernelGGL((k_fc0_fused<1, false>), grid, dim3(512), 0, s, fp);
+  if (fp.gp.fmt == FMT_FP16) hipLaunchKernelGGL((k_fc0_fused<0>), grid, dim3(512), 0, s, fp);
+  else if (terms == 3) hipLaunchKernelGGL((k_fc0_fused<3>), grid, dim3(512), 0, s, fp);
+  else hipLaunchKernelGGL((k_fc0_fused<1>), grid, dim3(512), 0, s, fp);
   return hipGetLastError();
 }
 

@@ -553,8 +553,12 @@ __device__ __forceinline__ void reduce_proj_exact(const typename M::Raw (&v)[4],
 // OUT32 (projected perceptual map, list_prep_percep_proj): the map holds H1 channels per pixel and the sample is
 // written as an fp32 row vector into the first bytes of the point's X row -- the perceptual block of X, which fc_0
 // then leaves out of its K loop and adds in its epilogue instead.  Out-of-map taps are masked like the reference.
-// `kept` (OUT32 only): the first `kept` channels of a pixel are sampled into X as without OUT32, the channels behind
+// `kept`, OUT32: the first `kept` channels of a pixel are sampled into X as without OUT32, the channels behind
 // them into the row vector (list_prep_img_proj: kept encoder levels | projected sum; list_prep_percep_proj: kept = 0).
+// `kept` > 0 without OUT32: ONLY the first `kept` of a pixel's Ct channels are sampled, into X columns col_off .. + kept
+// -- the kept levels of list_prep_img_proj's map for an fc_0 that samples the projected channels in its own epilogue
+// (gemm_kernels.hip, EPI_RELU_SAMPLE).  No lane exists for the other channels and no row vector is written; with
+// g.order_img == nullptr it runs in the order of the rows (Morton) and needs neither order_img nor row_of.
 template <int FMT, int F16, int OUT32 = 0>
 __global__ __launch_bounds__(256) void k_gather_img(GatherParams g, const void* __restrict__ img_map,
                                                     const float* __restrict__ trans_mat, int ms,
@@ -590,7 +594,7 @@ __global__ __launch_bounds__(256) void k_gather_img(GatherParams g, const void* 
   unsigned short* __restrict__ xl = g.x_lo;
   const int64_t img_stride = (int64_t)ms * ms * Ct;
   constexpr int NP = 2;                 // points in flight per lane: 4 * NP 16-B loads (measured best)
-  const int lq = Ct / M::V;             // lanes that cover one point
+  const int lq = ((!OUT32 && kept > 0) ? kept : Ct) / M::V;   // lanes that cover one point
   // a step covers `span` points: the workgroup's 256 lanes over (point, channel group), NP deep
   const int ppp = lq >= 256 ? 1 : 256 / lq;                 // points per pass of the workgroup
   const int span = ppp * NP;
@@ -629,7 +633,9 @@ __global__ __launch_bounds__(256) void k_gather_img(GatherParams g, const void* 
         // the perceptual block of a row is 2 KB of whole, line-aligned lines written once: non-temporal (round 4, two
         // interleaved pairs on one device: this kernel 0.244 -> 0.235 ms, gather group 0.850 -> 0.828, step -0.02 ms;
         // the 32 ... 256-B pieces of the voxel gathers keep the plain stores that merge in L2, list_common.h x_store)
-        store_feats<FMT, M::V, true>(xh, xl, (int64_t)a.row * g.Kp + col_off + q * M::V, r, a.valid != 0);
+        // (kept-only form: 128 ... 256-B pieces like a voxel level's, the plain stores of x_store)
+        if (!OUT32 && kept > 0) store_feats<FMT, M::V, false>(xh, xl, (int64_t)a.row * g.Kp + col_off + q * M::V, r, a.valid != 0);
+        else store_feats<FMT, M::V, true>(xh, xl, (int64_t)a.row * g.Kp + col_off + q * M::V, r, a.valid != 0);
       }
     }
   }
@@ -925,6 +931,12 @@ static hipError_t launch_gather_fmt(const GatherParams& g, const FeatLayout& L, 
       else
         LIST_LAUNCH((k_gather_img<FMT, 0, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.percep_proj,
                     a.trans_mat, a.map_size, a.H1, a.clamp_hi, 0, 0);
+    } else if (a.img_proj && !g.rowvec) {
+      // fc_0 samples the projected channels itself (EPI_RELU_SAMPLE): the kept channels only, in the order of the rows
+      if (FMT != FMT_FP16 || g.order_img) return hipErrorInvalidValue;
+      if (a.img_kept_C == 0) return hipSuccess;
+      LIST_LAUNCH((k_gather_img<FMT_FP16, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,
+                  a.trans_mat, a.map_size, a.img_kept_C + a.H1, a.clamp_hi, L.img_off, a.img_kept_C);
     } else if (a.img_proj) {      // list_prep_img_proj: img_kept_C sampled channels | H1 projected ones per pixel
       if (FMT == FMT_FP16)
         LIST_LAUNCH((k_gather_img<FMT, 1, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,

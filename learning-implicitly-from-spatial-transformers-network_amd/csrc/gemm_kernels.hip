@@ -21,11 +21,15 @@
 
 #include "list_common.h"
 #include "mfma_common.h"
+#include "point_math.h"
+#include "gather_math.h"
 
 namespace list {
 
 constexpr int BM = 256, BN = 256;
 constexpr int kLdsBytes = 131072;               // 128 KB of the CU's 160 KB
+// EPI_RELU_SAMPLE: the projections of the tile's 256 rows (RowProjRec, point_math.h), behind the operand stages
+constexpr int kProjRecBytes = BM * (int)sizeof(RowProjRec);     // 12 KB
 
 // Software pipeline.  A stage = the operand planes of one K-step:
 //   TERMS = 3 (bf16 hi/lo): {A_hi, A_lo, W_hi, W_lo}, BK = 32 (64-B rows),  4 x 16 KB, 2 stages;
@@ -449,6 +453,75 @@ __device__ __forceinline__ void gemm_epilogue16(const GemmParams& p, f32x4v (&ac
     });
     // NaN probe for the exact redo of the row tile's gathers (see gemm_epilogue)
     if (p.nan_tiles && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) p.nan_tiles[m0 / BM] = 1;
+  } else if constexpr (EPI == EPI_RELU_SAMPLE) {
+    // fc_0 on list_prep_img_proj's map (fp16): the projected levels' contribution is the bilinear sample of the map's
+    // N projected channels (p.smp_coff on: the kept channels lead a pixel), added to the K sum before bias and ReLU.  In
+    // the staged layout a thread owns (row, 8 consecutive columns) = (point, 8 consecutive projected channels): one 16-B
+    // load per tap, the four taps of a turn's four items requested before the turn's staging stores.  The rows'
+    // projections were left behind the operand stages by the kernel's prologue (RowProjRec).  No row-vector buffer.
+    // (Round 4b, on the 128 x 512 tile that carried this epilogue first: requesting turn c + 1's taps behind turn c's
+    // staging stores, two tap buffers, was SLOWER -- not round-trip latency, the bytes themselves.)
+    using M = MapT<1>;
+    const int64_t row_base = m0 + wm * 128;
+    const int col_base = n0 + wn * 64;
+    float* tile = (float*)smem + wave * (32 * kStageLd);
+    const int rr = lane >> 3, c8 = (lane & 7) * 8;
+    const RowProjRec* recs = (const RowProjRec*)(smem + kLdsBytes) + wm * 128;
+    const float4 b0 = *(const float4*)(p.bias + col_base + c8), b1 = *(const float4*)(p.bias + col_base + c8 + 4);
+    const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    bool bad = false;
+    __syncthreads();                                 // every wave is done with the operand stages; the records are complete
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      uint4 ptap[4][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const RowProjRec& rc = recs[c * 32 + rr + 8 * k];
+        const int64_t o = rc.base + p.smp_coff + col_base + c8;
+        ptap[k][0] = M::load(p.smp_map, o);
+        ptap[k][1] = M::load(p.smp_map, o + rc.dx);
+        ptap[k][2] = M::load(p.smp_map, o + rc.dy);
+        ptap[k][3] = M::load(p.smp_map, o + rc.dy + rc.dx);
+      }
+#pragma unroll
+      for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            tile[(ii * 16 + row_in + e) * kStageLd + j * 16 + col_in] = acc[2 * c + ii][j][e];
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int r = rr + 8 * k;
+        const float4 x = *(const float4*)(tile + r * kStageLd + c8);
+        const float4 y = *(const float4*)(tile + r * kStageLd + c8 + 4);
+        const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+        // the sample of (row, 8 channels): out-of-map taps masked like the reference (k_gather_img's OUT32 form,
+        // reduce_proj_exact), rows beyond the query contribute nothing; (acc + sample) + bias, the K sum first, as the
+        // row-vector epilogue above adds it: bit-identical to that pair
+        const RowProjRec& rc = recs[c * 32 + r];
+        const float wt[4] = {rc.w00, rc.w01, rc.w10, rc.w11};
+        float sm[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sm[e] = 0.f;
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) {
+          float f[8];
+          M::unpack(ptap[k][tp], f);
+          const bool dead = (rc.valid >> (1 + tp)) & 1;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) sm[e] = fmaf(dead ? 0.f : f[e], wt[tp], sm[e]);
+        }
+        const bool live = (rc.valid & 1) != 0;
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { o[e] = relu_nan((v[e] + (live ? sm[e] : 0.f)) + bb[e]); bad = bad || (o[e] != o[e]); }
+        store8_planes<FP16>(p.out_hi, p.out_lo, (row_base + c * 32 + r) * p.ldo + col_base + c8, o);
+      }
+      __syncthreads();
+    }
+    if (p.nan_tiles && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) p.nan_tiles[m0 / BM] = 1;
   } else if (EPI == EPI_MASK_SPLIT) {
     const int64_t row_base = m0 + wm * 128;
     const int col_base = n0 + wn * 64;
@@ -595,7 +668,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
   using P = Pipe<1>;
   static_assert(X3 == 0 || (S16 && !FP16), "interleaved split operands: 16x16x32 bf16 only");
   static_assert(P::BK == 64 && P::kRowBytes == 128, "single-plane pipeline");
-  __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
+  static_assert(EPI != EPI_RELU_SAMPLE || (S16 && FP16 && X3 == 0), "the sampling epilogue: fp16 on the 16x16x32 shape");
+  __shared__ __attribute__((aligned(16))) char smem[kLdsBytes + (EPI == EPI_RELU_SAMPLE ? kProjRecBytes : 0)];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -664,7 +738,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
       const int row = row0 + lane / 8;
       const int chunk = (lane % 8) ^ P::swz(row);
       const char* g = (is_a ? A + (int64_t)min(m0 + row, a_last) * lda : Wt + (int64_t)(n0 + row) * ldw) + kbyte + chunk * 16;
-      if (EPI == EPI_RELU_SPLIT && is_a) glds16_nt(g, sbase + row0 * P::kRowBytes);
+      if ((EPI == EPI_RELU_SPLIT || EPI == EPI_RELU_SAMPLE) && is_a) glds16_nt(g, sbase + row0 * P::kRowBytes);
       else glds16(g, sbase + (is_a ? 0 : P::kWOff) + row0 * P::kRowBytes);
     }
   };
@@ -681,6 +755,13 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_pp(GemmParams p) {
 #pragma unroll
   for (int g = 0; g < kLead; ++g)
     if (g / 4 < nk) stage_quarter(smem + ((g / 4) & 1) * P::kStageBytes, ktb(g / 4), g & 3);
+  if constexpr (EPI == EPI_RELU_SAMPLE) {
+    // the projections of the tile's rows for the epilogue, one per thread of the first wave group, while the first
+    // K-tile is on its way: nothing of them stays in registers across the K loop
+    if (wm == 0)
+      *((RowProjRec*)(smem + kLdsBytes) + threadIdx.x) =
+          row_proj_rec(p.smp_pts, p.smp_trans_mat, p.smp_ms, p.smp_Ct, p.smp_clamp_hi, m0 + (int)threadIdx.x);
+  }
   if (nk > 1) wait_vmcnt<2 * (kLead - 4)>(); else wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();
@@ -1066,6 +1147,14 @@ static hipError_t launch_epi(const GemmParams& p, int epi, hipStream_t s) {
 }
 
 hipError_t launch_gemm(const GemmParams& p, int terms, int epi, hipStream_t s) {
+  if (epi == EPI_RELU_SAMPLE) {  // one instantiation: fp16 operands, the ping-pong schedule on the 16x16x32 shape
+    if (p.fmt != FMT_FP16 || p.x3i || p.n_groups || p.rowvec || p.plain_loop || !p.bias || !p.smp_map || !p.smp_trans_mat ||
+        !p.smp_pts.query || p.smp_ms < 2 || p.smp_coff < 0 || p.smp_coff % 8 || p.smp_Ct % 8 || p.smp_coff + p.N > p.smp_Ct ||
+        p.M % BM || p.N % BN || p.K % 64 || p.M <= 0 || p.K <= 0)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_gemm_nt_pp<EPI_RELU_SAMPLE, 1, true>), dim3((p.M / BM) * (p.N / BN)), dim3(512), 0, s, p);
+    return hipGetLastError();
+  }
   if (p.n_groups) {            // grouped launch: every group on its own terms, together M row tiles
     if (epi != EPI_DX || p.n_groups < 0 || p.n_groups > kGemmMaxGroups) return hipErrorInvalidValue;
     int tiles = 0;

@@ -165,12 +165,19 @@ int fused_fc0_mode() {
   }();
   return mode;
 }
-bool takes_fused_fc0_any(const ListQueryArgs* a, const FeatLayout& L) {
+// What the call sites ask (each its own question; the answers coincide on some paths only):
+//   runs_fc0_fused_kernel   : fc_0 is the 128 x 512 kernel (k_fc0_fused)
+//   runs_fc0_sampled        : fc_0 is the 256 x 256 ping-pong kernel with the sampling epilogue (EPI_RELU_SAMPLE), behind
+//                             the kept-channels-only 2-D gather: fp16 inference forwards on list_prep_img_proj's map
+//   fc0_samples_map         : fc_0 samples the perceptual map itself -- no row-vector buffer, no pixel order in the sort;
+//                             what list_query_plan reports as fused_fc0
+//   skips_img_gather        : no 2-D gather launch at all (every perceptual column of X is produced inside fc_0)
+bool runs_fc0_fused_kernel(const ListQueryArgs* a, const FeatLayout& L) {
   if (fused_fc0_mode() == 0) return false;
   if (a->percep_feat || a->percep_proj) return false;
-  // list_prep_img_proj's map: the kept levels are produced on chip, the projected channels sampled in the epilogue
-  // (k_fc0_fused<0, true>: fp16 operands only)
-  if (a->img_proj && (a->precision != LIST_PREC_FP16 || fused_fc0_mode() == 2)) return false;
+  // list_prep_img_proj's map leaves 2 perceptual K-tiles of 43: not worth the 128-row tile (runs_fc0_sampled, or the
+  // row-vector pair)
+  if (a->img_proj) return false;
   // fp16 operands with fp16 maps, the bf16 formats with fp32 maps (the pairs the standard path takes too)
   if ((a->precision == LIST_PREC_FP16) != (a->img_dtype == LIST_MAP_F16)) return false;
   // bf16x3 keeps the unfused path: its packed weight is twice as long (hi + lo), and a 128-row tile streams ALL of it
@@ -183,12 +190,19 @@ bool takes_fused_fc0_any(const ListQueryArgs* a, const FeatLayout& L) {
   return a->H1 == 512 && a->img_C > 0 && a->img_C % 64 == 0 && L.img_off == 0 && L.Kp % 64 == 0;
 }
 int fused_produced_tiles(const ListQueryArgs* a) {
-  const int channels = a->img_proj ? a->img_kept_C : a->img_C;
-  return fused_fc0_mode() == 2 ? 0 : channels / (a->precision == LIST_PREC_FP16 ? 64 : 32);
+  return fused_fc0_mode() == 2 ? 0 : a->img_C / (a->precision == LIST_PREC_FP16 ? 64 : 32);
 }
-// true: the 2-D gather kernel is NOT launched (its columns are produced inside fc_0)
-bool takes_fused_fc0(const ListQueryArgs* a, const FeatLayout& L) {
-  return takes_fused_fc0_any(a, L) && fused_fc0_mode() != 2;
+bool skips_img_gather(const ListQueryArgs* a, const FeatLayout& L) {
+  return runs_fc0_fused_kernel(a, L) && fused_fc0_mode() != 2;
+}
+bool runs_fc0_sampled(const ListQueryArgs* a, const FeatLayout& L) {
+  // (LIST_FUSED_FC0=0 / x keep the row-vector pair here too, as they keep the unfused pair on the standard path)
+  if (!a->img_proj || a->precision != LIST_PREC_FP16 || a->img_dtype != LIST_MAP_F16) return false;
+  if (fused_fc0_mode() == 0 || fused_fc0_mode() == 2 || !a->no_activations || a->no_fused_fc0) return false;
+  return a->H1 == 512 && a->img_C % 64 == 0 && L.img_off == 0 && L.Kp % 64 == 0;
+}
+bool fc0_samples_map(const ListQueryArgs* a, const FeatLayout& L) {
+  return skips_img_gather(a, L) || runs_fc0_sampled(a, L);
 }
 
 // inference forwards in fp16: fc_1, fc_2 and fc_out as ONE launch (gemm_kernels.hip, k_mlp_tail_f16).  The one
@@ -605,9 +619,10 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     if (!a->no_sort) {
       SortBuffers sb;
       // the pixel order serves the 2-D gather kernel (and, behind a training forward, the backward's map-side gather):
-      // a forward whose fc_0 samples the map itself (k_fc0_fused) sorts by Morton cell only -- no projection per point,
-      // half the counters, one scan and two index arrays less
-      const bool want_pix = !takes_fused_fc0(a, L);
+      // a forward whose fc_0 samples the map itself (k_fc0_fused, or the sampling epilogue behind the kept-channels gather,
+      // which runs in Morton order) sorts by Morton cell only -- no projection per point, half the counters, one scan and
+      // two index arrays less
+      const bool want_pix = !fc0_samples_map(a, L);
       sb.order = (int*)(wsb + ws.order); sb.order_img = want_pix ? (int*)(wsb + ws.order_img) : nullptr;
       sb.row_of = (int*)(wsb + ws.row_of); sb.keys = (int*)(wsb + ws.keys);
       sb.keys2 = (int*)(wsb + ws.keys2); sb.bins = (int*)(wsb + ws.bins);
@@ -620,8 +635,15 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     }
     mark(LIST_STAGE_SORT);
     int* nan_tiles = (int*)(wsb + ws.nan_tiles);
-    const bool fused0 = takes_fused_fc0_any(a, L);            // the 128 x 512 kernel runs
-    e = launch_gather(g, L, chunk_args, nan_tiles, s, /*skip_img=*/takes_fused_fc0(a, L));
+    const bool fused0 = runs_fc0_fused_kernel(a, L);
+    const bool sampled0 = runs_fc0_sampled(a, L);
+    {
+      // sampled0: no row vectors from the 2-D gather -- it samples the kept channels only (the fix-up below still
+      // writes the row vectors of the tiles it redoes, for the gated re-run)
+      GatherParams gg = g;
+      if (sampled0) gg.rowvec = nullptr;
+      e = launch_gather(gg, L, chunk_args, nan_tiles, s, /*skip_img=*/skips_img_gather(a, L));
+    }
     if (e != hipSuccess) return hip_fail(e, "gather launch");
     mark(LIST_STAGE_TAIL);
 
@@ -667,15 +689,18 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
       FusedFc0Params fp;
       fp.gp = gp; fp.g = g; fp.img_map = a->img_map; fp.trans_mat = a->trans_mat;
       fp.ms = a->map_size; fp.Ct = a->img_C; fp.clamp_hi = a->clamp_hi; fp.n_produced = fused_produced_tiles(a);
-      fp.proj = 0; fp.kept = 0;
-      if (a->img_proj) {
-        // the kernel samples the projected channels itself (no row-vector buffer); the exact redo below takes the row
-        // vectors the fix-up kernel writes for the tiles it flags
-        fp.proj = 1; fp.kept = a->img_kept_C; fp.Ct = a->img_kept_C + a->H1; fp.gp.rowvec = nullptr;
-      }
-      if (!fused_fc0_eligible(fp.gp, a->img_dtype == LIST_MAP_F16, a->img_proj ? a->img_kept_C : a->img_C))
+      if (!fused_fc0_eligible(fp.gp, a->img_dtype == LIST_MAP_F16, a->img_C))
         return fail(LIST_ERR_ARG, "internal: fused fc_0 taken for arguments it does not support");
       e = launch_fc0_fused(fp, terms, s);
+    } else if (sampled0) {
+      // the kept levels' K-tiles come from X like every other tile; the epilogue samples the projected channels from
+      // the map (no row-vector buffer).  The exact redo below takes the row vectors the fix-up kernel writes for the
+      // tiles it flags.
+      GemmParams sp = gp;
+      sp.rowvec = nullptr; sp.rowvec_stride = 0;
+      sp.smp_map = a->img_map; sp.smp_trans_mat = a->trans_mat; sp.smp_ms = a->map_size;
+      sp.smp_Ct = a->img_kept_C + a->H1; sp.smp_coff = a->img_kept_C; sp.smp_clamp_hi = a->clamp_hi; sp.smp_pts = g;
+      e = launch_gemm(sp, terms, EPI_RELU_SAMPLE, s);
     } else {
       e = launch_gemm(gp, terms, EPI_RELU_SPLIT, s);
     }
@@ -751,7 +776,7 @@ int list_query_plan(const ListQueryArgs* a, ListQueryPlan* plan) {
     const int n_valid = (int)(P < rows ? P : rows);
     const GatherParams g = make_gather(a, L, ws, 0, n_valid, (n_valid + kRowTile - 1) / kRowTile * kRowTile);
     plan->box_levels = gather_box_levels(g, L, *a);
-    plan->fused_fc0 = takes_fused_fc0(a, L) ? 1 : 0;
+    plan->fused_fc0 = fc0_samples_map(a, L) ? 1 : 0;
   }
   return LIST_OK;
 }

@@ -408,11 +408,18 @@ struct GemmParams {
   int k_gap_at, k_gap;                                       // K-tiles (128 operand bytes per row) k_gap_at .. are read k_gap tiles further on in
                                                              //   A and W: fc_0 without the PROJECTED levels of its perceptual block
                                                              //   (list_prep_img_proj); K counts the tiles that are read.  0 / 0: none
+  // EPI_RELU_SAMPLE (ping-pong kernel, fp16): the epilogue adds the bilinear sample of N channels of a prepared map to
+  // the accumulators before bias and ReLU -- the projected channels of list_prep_img_proj's map, for the points behind the rows
+  const void* smp_map;                                       // [B][smp_ms][smp_ms][smp_Ct] halfs
+  const float* smp_trans_mat;                                // [B][4][3]
+  int smp_ms, smp_Ct, smp_coff; float smp_clamp_hi;          // map size, channels per pixel, first sampled channel (the kept ones lead)
+  GatherParams smp_pts;                                      // the points behind the rows (query, order, perm, scale, N, p_begin, n_valid)
 };
 
 // EPI_MASK_SPLIT: out = acc where the saved activation is positive (ReLU backward), no bias;
 // EPI_DX: plain store of acc (fp16 or fp32) with a column guard (N is padded to the tile).
-enum { EPI_RELU_SPLIT = 0, EPI_F32 = 1, EPI_RELU_DOT = 2, EPI_MASK_SPLIT = 3, EPI_DX = 4 };
+// EPI_RELU_SAMPLE: EPI_RELU_SPLIT with the sample of GemmParams.smp_map added before the bias (fp16, ping-pong kernel).
+enum { EPI_RELU_SPLIT = 0, EPI_F32 = 1, EPI_RELU_DOT = 2, EPI_MASK_SPLIT = 3, EPI_DX = 4, EPI_RELU_SAMPLE = 5 };
 
 // out[m][n] = sum_p A[p][m] * B[p][n]  (weight gradients: A = dZ, B = X / H); split over p into slabs
 struct GemmTnParams {
@@ -452,6 +459,8 @@ hipError_t launch_sort_points(const GatherParams& g, const ListQueryArgs& a, con
                               hipStream_t s);
 // nan_tiles: int32 [rows / 256], cleared by the last gather kernel (the flags of fc_0's NaN probe)
 // skip_img: the 2-D gather is left out (its columns of X are produced inside the fused fc_0, fused_fc0_kernels.hip)
+// img_proj without g.rowvec: the 2-D gather samples the kept channels only, in the order of the rows (fc_0's epilogue
+// samples the projected ones, EPI_RELU_SAMPLE)
 hipError_t launch_gather(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a,
                          int* nan_tiles, hipStream_t s, bool skip_img = false);
 hipError_t launch_features_out(const GatherParams& g, const FeatLayout& L, float* out, int* nan_tiles,
@@ -475,9 +484,6 @@ struct FusedFc0Params {
   int ms, Ct; float clamp_hi;
   int n_produced;                // leading K-tiles produced on chip (Ct / 64, or Ct / 32 in the bf16 formats); 0: every
                                  //   K-tile from X (tile-shape diagnostic)
-  int proj, kept;                // proj = 1 (list_prep_img_proj's map, fp16 operands): Ct = kept + N channels per pixel,
-                                 //   n_produced = kept / 64, gp.k_gap_at / k_gap leave the projected levels' K-tiles out and
-                                 //   the epilogue adds the sample of the N projected channels
 };
 bool fused_fc0_eligible(const GemmParams& gp, int img_f16, int img_C);
 hipError_t launch_fc0_fused(const FusedFc0Params& fp, int terms, hipStream_t s);

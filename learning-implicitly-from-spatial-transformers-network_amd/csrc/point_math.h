@@ -122,4 +122,23 @@ __device__ __forceinline__ Proj project(const float* __restrict__ T, float px, f
   return r;
 }
 
+// One row's projection packed for the kernels that sample the prepared map themselves (fused_fc0_kernels.hip: the
+// produced K-tiles; gemm_kernels.hip: the sampling epilogue): element offset of tap 00 in the whole map, the steps to
+// the +x / +y taps (o11 = o00 + dx + dy: x1, y1 are clamped separately), the four weights, and
+// valid: bit 0 = the row is a query point, bits 1..4 = Proj::dead, the taps outside the map.  48 B: three 16-B LDS reads.
+struct RowProjRec { int64_t base; int dx, dy; float w00, w01, w10, w11; int valid, pad_[3]; };
+
+__device__ __forceinline__ RowProjRec row_proj_rec(const GatherParams& g, const float* __restrict__ trans_mat, int ms,
+                                                   int Ct, float clamp_hi, int row) {
+  const Pt pt = load_point(g, row);
+  const Proj q = project(trans_mat + pt.b * 12, pt.x, pt.y, pt.z, ms, Ct, clamp_hi);
+  RowProjRec r;
+  r.base = (int64_t)pt.b * ms * ms * Ct + q.o00;
+  r.dx = q.o01 - q.o00; r.dy = q.o10 - q.o00;
+  r.w00 = q.w00; r.w01 = q.w01; r.w10 = q.w10; r.w11 = q.w11;
+  r.valid = (pt.valid ? 1 : 0) | (q.dead << 1);
+  r.pad_[0] = r.pad_[1] = r.pad_[2] = 0;
+  return r;
+}
+
 }  // namespace list
