@@ -1,25 +1,26 @@
 // Adjoint of the matrix-core gather of a coarse voxel level (gather_box_kernels.hip; the reference's autograd of
-// network/modules.py:256-265 for the 16^3 and 8^3 x 128-channel levels), fp16 operands: the gradient of the voxel box that a run
+// network/modules.py:256-265 for the 16^3 and 8^3 x 128-channel levels): the gradient of the voxel box that a run
 // of Morton-consecutive points touches is ONE small dense product on the matrix cores,
 //   dV^T[c][v] = sum_k dX^T[c][k] * Wt[k][v],   k = (point, stencil slot j = 0..6 and a zero slot),  v = box row,
-//   v_mfma_f32_16x16x32_f16: one K-step = 4 points x 8 slots,
+//   one K-step of a 16x16x32 MFMA = 4 points x 8 slots,
 // instead of the read-add-write chain of k_scatter_vox_win (bwd_scatter_kernels.hip) that sums the same terms on the
 // VALU, one point and one window slot at a time.  Wt is 94 % zeros (8 taps of <= 128 box rows) and that does not matter:
 // the dense product of a workgroup is 15 - 30 MFLOP, a few thousand matrix-core cycles.
-//   A = dX^T: the run's dX rows are copied to LDS as they lie in memory ([sample][128 halfs], 16-B chunks XOR-swizzled
-//       by the stencil slot, 8-B halfs swapped for odd points) and read with ds_read_b64_tr_b16, like the forward's V^T;
+//   A = dX^T: the run's dX rows are copied to LDS as 16-bit images ([sample][128], 16-B chunks XOR-swizzled by the
+//       stencil slot, 8-B halfs swapped for odd points) and read with ds_read_b64_tr_b16, like the forward's V^T;
 //   B = Wt:   formed per lane in the B-fragment layout -- a lane owns ONE box row (its voxel) and the 8 slots of ONE point
 //       per K-step, so its 8 values are products of three per-axis factors looked up by comparing the voxel's coordinates
-//       with the point's nine axis records; split hi + lo in fp16 so that the products are exact in the fp32 accumulator
-//       (same interpolation arithmetic as the VALU kernels up to the order of the fp32 sums);
+//       with the point's nine axis records; split hi + lo in the operand's 16-bit format so that the products are exact in
+//       the fp32 accumulator (same interpolation arithmetic as the VALU kernels up to the order of the fp32 sums);
 //   D:        wave w accumulates box-row tiles w and w + 4 (16 rows each) x all 128 channels, 64 accumulator registers.
-// The finished box goes through LDS once more ([row][128 halfs] at the window scale kWinPkScale) so that the flush is the
-// one k_scatter_vox_win has: packed-half atomics, lanes over channel pairs, whole 256-B rows per instruction.
+// One kernel body, three instantiations: what the element type of dX decides (staged image, 16-bit format, MFMA sequence,
+// LDS region, flush) is an operand policy below -- fp16 with the packed-half flush, fp16 with the diagnostic fp32 flush,
+// and fp32 dX as bf16 hi + lo.
 //
 // Workgroup = 64 consecutive rows (Morton order), 256 threads; runs = the forward's aligned power-of-two runs whose box
 // has at most 128 rows (a single point's 4 x 4 x 4 always fits; at 16^3 that is ~8 points per run).
 //
-// Measured (config 2, 160 000 points, in-line backward, rocprofv3 kernel trace): 16^3 level 0.519 -> 0.224 ms, 8^3 level
+// Measured (fp16 form, config 2, 160 000 points, in-line backward, rocprofv3 kernel trace): 16^3 level 0.519 -> 0.224 ms, 8^3 level
 // 0.28 -> 0.118 ms against k_scatter_vox_win; of the 0.239 ms it took before its row -> voxel divisions became multiply-shifts
 // (0.224 now) the flush was 0.085 (exposed), the K loop 0.114 -- the weights
 // on the VALU more than the 32 MFMAs of a K-step: hi-only weights save 0.02; the per-axis factors read from per-point
@@ -28,6 +29,7 @@
 #include "list_common.h"
 #include "point_math.h"
 #include "box_partition.h"
+#include "mfma_common.h"
 
 namespace list {
 
@@ -35,32 +37,253 @@ constexpr int kAdjPts = 64;                       // points per workgroup
 constexpr int kAdjRows = 128;                     // box rows (8 tiles of 16: two per wave)
 constexpr int kAdjChunkPts = 8;                   // points staged per chunk (two K-steps)
 constexpr int kAdjC = 128;
+constexpr int kAdjNT = kAdjC / 16;                // 16-channel tiles
 constexpr float kAdjPkScale = 0.0625f;            // = kWinPkScale of bwd_scatter_kernels.hip (asserted by the launcher)
+constexpr int kAdjRowBytes = 2 * kAdjC;                                  // 256: one 16-bit plane of a staged row
+constexpr int kAdjStageRows = kAdjChunkPts * LIST_N_STENCIL;             // 56
+constexpr int kAdjPlaneBytes = kAdjStageRows * kAdjRowBytes;             // 14336
 
-struct AdjLds {
-  static constexpr int kRowBytes = 2 * kAdjC;                                   // 256
-  static constexpr int kStageRows = kAdjChunkPts * LIST_N_STENCIL;              // 56
-  static constexpr int stage = 0;                                               // 2 x [56][256 B]; later the box [128][256 B]
-  static constexpr int stage_bytes = kStageRows * kRowBytes;                    // 14336
-  static constexpr int region = kAdjRows * kRowBytes;                           // 32768 >= 2 * stage_bytes
-  static constexpr int zero = region;                                           // one row of zeros
-  static constexpr int ptab = zero + kRowBytes;                                 // AxisW [64][3 axes][3 variants]
+// LDS: the operand's region (two staging buffers; later the finished box), then the tables every form has
+template <int REGION> struct AdjLds {
+  static constexpr int stage = 0;
+  static constexpr int zero = REGION;                                           // one row of zeros
+  static constexpr int ptab = zero + kAdjRowBytes;                              // AxisW [64][3 axes][3 variants]
   static constexpr int run = ptab + kAdjPts * 9 * (int)sizeof(AxisW);           // RunBox [64]
   static constexpr int pbox = run + kAdjPts * (int)sizeof(RunBox);              // int [64][4]
   static constexpr int total = pbox + kAdjPts * 16;
 };
-static_assert(2 * AdjLds::stage_bytes <= AdjLds::region, "the two staging buffers share the box's LDS");
 
-// grid = rows / 64, block = 256.  img16: the level's zeroed fp16 image (gradient scale x kAdjPkScale).
+// global address of box row (ix, iy, iz) of the run's image, in elements of 128-channel rows
+__device__ __forceinline__ int64_t adj_voxel(const RunDims& d, const ListVoxLevel& gv, int ix, int iy, int iz) {
+  return ((int64_t)((d.loz + iz) * gv.H + (d.loy + iy)) * gv.W + (d.lox + ix)) * kAdjC;
+}
+
+// ---- operand policies: what the element type of dX decides -- the staged image, the weights' 16-bit format, the MFMA
+// sequence of a K-step and the flush.  Runs, tiles, lane roles and the weights' arithmetic are the kernel's. -----------
+
+// fp16 dX.  A = dX^T: the rows are copied to LDS as they lie in memory ([sample][128 halfs]).  The finished box goes
+// through LDS once more ([row][128 halfs] at the window scale kAdjPkScale) so that the flush is the one
+// k_scatter_vox_win has: packed-half atomics into img16, the level's zeroed fp16 image, lanes over channel pairs, whole
+// 256-B rows per instruction.
 // F32OUT (diagnostic, LIST_SCATTER_F32=1): the accumulators go straight to the level's zeroed fp32 gradient as float
 // atomics, unrounded -- the form tests/test_box_adjoint_gpu.py compares with the window kernel's fp32 flush at 2e-5.
+template <int F32OUT> struct AdjF16 {
+  static constexpr int kBufBytes = kAdjPlaneBytes;                              // 2 x [56][256 B]
+  static constexpr int kRegion = kAdjRows * kAdjRowBytes;                       // 32768: the box [128][256 B]
+  static constexpr bool kScaleInFlush = F32OUT;                                 // 1 / s is read per run (diagnostic form only)
+  using L = AdjLds<kRegion>;
+  typedef unsigned short Elem;
+  typedef uint4 Piece;                                                          // 8 channels of a staged row
+
+  static __device__ __forceinline__ Piece no_piece() { return make_uint4(0u, 0u, 0u, 0u); }
+  static __device__ __forceinline__ Piece load_piece(const Elem* src) { return *(const uint4*)src; }
+  static __device__ __forceinline__ void store_piece(char* buf, int off, bool odd, const Piece& p) {
+    *(uint4*)(buf + off) = odd ? make_uint4(p.z, p.w, p.x, p.y) : p;
+  }
+  static __device__ __forceinline__ unsigned pk2(float a, float b) { return pk_h2(a, b); }
+  static __device__ __forceinline__ float up(unsigned short h) { return h2f(h); }
+
+  // A of a K-step: every transposed read at once, ahead of the weights' VALU work
+  struct AFrag { s16x4 a0[kAdjNT], a1[kAdjNT]; };
+  static __device__ __forceinline__ AFrag a_frags(const char* a_lo, const char* a_hi, bool, bool, const int (&aoff)[kAdjNT]) {
+    AFrag f;
+#pragma unroll
+    for (int t = 0; t < kAdjNT; ++t) {
+      f.a0[t] = tr_read16(a_lo + aoff[t]);
+      f.a1[t] = tr_read16(a_hi + aoff[t]);
+    }
+    return f;
+  }
+  static __device__ __forceinline__ void mma(const AFrag& f, const int (&)[kAdjNT], const uint4 (&bhi)[2], const uint4 (&blo)[2],
+                                             bool own0, bool own1, f32x4v (&acc)[2][kAdjNT]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (i == 0 ? !own0 : !own1) continue;
+      const f16x8 bh = __builtin_bit_cast(f16x8, bhi[i]), bl = __builtin_bit_cast(f16x8, blo[i]);
+#pragma unroll
+      for (int t = 0; t < kAdjNT; ++t) {
+        const f16x8 a = __builtin_bit_cast(f16x8, (s16x8){f.a0[t][0], f.a0[t][1], f.a0[t][2], f.a0[t][3], f.a1[t][0], f.a1[t][1], f.a1[t][2], f.a1[t][3]});
+        acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bh, acc[i][t], 0, 0, 0);
+      }
+      // the lo plane of the weights: rounding them to fp16 alone would save 16^3 level 0.253 -> 0.230 ms -- not
+      // worth the exactness
+#pragma unroll
+      for (int t = 0; t < kAdjNT; ++t) {
+        const f16x8 a = __builtin_bit_cast(f16x8, (s16x8){f.a0[t][0], f.a0[t][1], f.a0[t][2], f.a0[t][3], f.a1[t][0], f.a1[t][1], f.a1[t][2], f.a1[t][3]});
+        acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bl, acc[i][t], 0, 0, 0);
+      }
+    }
+  }
+
+  // D: column = box row (lane & 15), rows 4 q + reg of tile t = channels 32 (t >> 1) + 8 q + 4 (t & 1) + reg
+  static __device__ __forceinline__ void flush(char* smem, const f32x4v (&acc)[2][kAdjNT], const RunDims& d, int rb_b, int wave,
+                                               int lane, bool own0, bool own1, const ListVoxLevel& gv, float inv_s,
+                                               _Float16* __restrict__ img16) {
+    const int q = lane >> 4, col = lane & 15;
+    if (F32OUT) {
+      float* base = (float*)gv.data + (int64_t)rb_b * gv.image_stride;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        if (i == 0 ? !own0 : !own1) continue;
+        const int v = 16 * (wave + 4 * i) + col;
+        if (v >= d.rows) continue;
+        int ix, iy, iz;
+        d.row_to_xyz(v, ix, iy, iz);
+        float* dst = base + adj_voxel(d, gv, ix, iy, iz);
+#pragma unroll
+        for (int t = 0; t < kAdjNT; ++t)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float val = acc[i][t][e];
+            if (val != 0.f) atomicAdd(dst + 32 * (t >> 1) + 8 * q + 4 * (t & 1) + e, val * inv_s);
+          }
+      }
+      return;
+    }
+    __syncthreads();                   // every wave is done with the staging buffers: the box takes their place
+    // 16-B pieces of 8 consecutive channels, chunk XOR (row & 15) (the 16 rows of a tile land on distinct banks)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (i == 0 ? !own0 : !own1) continue;
+      const int v = 16 * (wave + 4 * i) + col;
+#pragma unroll
+      for (int u = 0; u < kAdjNT / 2; ++u) {
+        const f32x4v c0 = acc[i][2 * u], c1 = acc[i][2 * u + 1];
+        const uint2 lo = half4_inrange(make_float4(c0[0] * kAdjPkScale, c0[1] * kAdjPkScale, c0[2] * kAdjPkScale, c0[3] * kAdjPkScale));
+        const uint2 hi = half4_inrange(make_float4(c1[0] * kAdjPkScale, c1[1] * kAdjPkScale, c1[2] * kAdjPkScale, c1[3] * kAdjPkScale));
+        *(uint4*)(smem + L::stage + v * kAdjRowBytes + (((4 * u + q) ^ col) << 4)) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+      }
+    }
+    __syncthreads();
+    // flush: lanes over channel pairs, one box row per wave and pass (its voxel address is scalar arithmetic) -- 256
+    // contiguous bytes per atomic instruction (its share: 16^3 level 0.239 -> 0.154 ms, 8^3 0.118 -> 0.104 without it)
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    _Float16* base16 = img16 + (int64_t)rb_b * gv.image_stride;
+#pragma unroll 1
+    for (int v = wave; v < d.rows; v += 4) {
+      int ix, iy, iz;
+      d.row_to_xyz(v, ix, iy, iz);
+      const unsigned bits = *(const unsigned*)(smem + L::stage + v * kAdjRowBytes + ((((lane >> 2) ^ (v & 15)) << 4) | ((lane & 3) << 2)));
+      if ((bits & 0x7fff7fffu) == 0u) continue;
+      __builtin_amdgcn_global_atomic_fadd_v2f16(
+          (__attribute__((address_space(1))) half2v*)(base16 + adj_voxel(d, gv, ix, iy, iz) + 2 * lane),
+          __builtin_bit_cast(half2v, bits));
+    }
+  }
+};
+
+// fp32 dX (bf16x3, bf16): BOTH operands split into bf16 hi + lo planes and three MFMAs per product (hi * hi + hi * lo +
+// lo * hi on v_mfma_f32_16x16x32_bf16: 16 mantissa bits per operand, the grade of the forward's bf16x3 products), the box
+// accumulated in fp32 and flushed as float atomics into the level's zeroed gradient -- 256 contiguous bytes per
+// instruction, like k_scatter_vox_win's fp32 flush.
+//   staging: the dX rows of 8 points are loaded as fp32, split, and written as two [sample][128] bf16 images (the fp16
+//            form's swizzle), the next chunk's fp32 pieces requested a chunk ahead (32 registers);
+//   LDS:     64 KB for the fp32 box (the 2 x 2 staging images share it) + 8.5 KB of tables: two workgroups per CU.
+struct AdjSplit {
+  static constexpr int kBufBytes = 2 * kAdjPlaneBytes;                          // 2 buffers x (hi | lo)
+  static constexpr int kRegion = kAdjRows * kAdjC * 4;                          // 65536: the fp32 box
+  static constexpr bool kScaleInFlush = false;                                  // 1 / s is read once per workgroup
+  using L = AdjLds<kRegion>;
+  typedef float Elem;
+  struct Piece { float4 a, b; };                                                // 8 channels: 32 B of fp32 in
+
+  static __device__ __forceinline__ Piece no_piece() { return {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)}; }
+  static __device__ __forceinline__ Piece load_piece(const Elem* src) { return {*(const float4*)src, *(const float4*)(src + 4)}; }
+  // 16 B of hi and 16 B of lo out
+  static __device__ __forceinline__ void store_piece(char* buf, int off, bool odd, const Piece& p) {
+    uint2 h0, h1, l0, l1;
+    split4(p.a, h0, l0);
+    split4(p.b, h1, l1);
+    *(uint4*)(buf + off) = odd ? make_uint4(h1.x, h1.y, h0.x, h0.y) : make_uint4(h0.x, h0.y, h1.x, h1.y);
+    *(uint4*)(buf + kAdjPlaneBytes + off) = odd ? make_uint4(l1.x, l1.y, l0.x, l0.y) : make_uint4(l0.x, l0.y, l1.x, l1.y);
+  }
+  static __device__ __forceinline__ unsigned pk2(float a, float b) { return (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16); }
+  static __device__ __forceinline__ float up(unsigned short h) { return bf2f(h); }
+
+  // A of a K-step: addresses only -- the fragments are read per channel half inside mma()
+  struct AFrag { const char *lo4, *hi4; int lo_plane, lo_plane_hi4; };
+  static __device__ __forceinline__ AFrag a_frags(const char* a_lo, const char* a_hi, bool live_lo, bool live_hi, const int (&)[kAdjNT]) {
+    return {a_lo, a_hi, live_lo ? kAdjPlaneBytes : 0, live_hi ? kAdjPlaneBytes : 0};      // (the zero row has no second plane)
+  }
+  static __device__ __forceinline__ void mma(const AFrag& f, const int (&aoff)[kAdjNT], const uint4 (&bhi)[2], const uint4 (&blo)[2],
+                                             bool own0, bool own1, f32x4v (&acc)[2][kAdjNT]) {
+    constexpr int NT = kAdjNT;
+    // the channel tiles in two halves (their hi and lo fragments are 32 registers per half)
+#pragma unroll
+    for (int th = 0; th < 2; ++th) {
+      bf16x8 ah[NT / 2], al[NT / 2];
+#pragma unroll
+      for (int tt = 0; tt < NT / 2; ++tt) {
+        const int t = th * (NT / 2) + tt;
+        const s16x4 h0 = tr_read16(f.lo4 + aoff[t]), h1 = tr_read16(f.hi4 + aoff[t]);
+        const s16x4 l0 = tr_read16(f.lo4 + f.lo_plane + aoff[t]), l1 = tr_read16(f.hi4 + f.lo_plane_hi4 + aoff[t]);
+        ah[tt] = __builtin_bit_cast(bf16x8, (s16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]});
+        al[tt] = __builtin_bit_cast(bf16x8, (s16x8){l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]});
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        if (i == 0 ? !own0 : !own1) continue;
+        const bf16x8 bh = __builtin_bit_cast(bf16x8, bhi[i]), bl = __builtin_bit_cast(bf16x8, blo[i]);
+#pragma unroll
+        for (int tt = 0; tt < NT / 2; ++tt) {
+          const int t = th * (NT / 2) + tt;
+          acc[i][t] = mfma16<0>(al[tt], bh, acc[i][t]);
+          acc[i][t] = mfma16<0>(ah[tt], bl, acc[i][t]);
+          acc[i][t] = mfma16<0>(ah[tt], bh, acc[i][t]);
+        }
+      }
+    }
+  }
+
+  static __device__ __forceinline__ void flush(char* smem, const f32x4v (&acc)[2][kAdjNT], const RunDims& d, int rb_b, int wave,
+                                               int lane, bool own0, bool own1, const ListVoxLevel& gv, float inv_s, _Float16*) {
+    const int q = lane >> 4, col = lane & 15;
+    __syncthreads();                   // every wave is done with the staging images: the fp32 box takes their place
+    // D: column = box row (lane & 15), rows 4 q + reg of tile t = channels 32 (t >> 1) + 8 q + 4 (t & 1) + reg -> one 16-B
+    // piece of 4 channels per tile: chunk 8 (t >> 1) + 2 q + (t & 1) of the row's 32, XOR (row & 31)
+    float* box = (float*)(smem + L::stage);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (i == 0 ? !own0 : !own1) continue;
+      const int v = 16 * (wave + 4 * i) + col;
+#pragma unroll
+      for (int t = 0; t < kAdjNT; ++t) {
+        const int chunk = (8 * (t >> 1) + 2 * q + (t & 1)) ^ (v & 31);
+        *(float4*)(box + v * kAdjC + chunk * 4) = make_float4(acc[i][t][0], acc[i][t][1], acc[i][t][2], acc[i][t][3]);
+      }
+    }
+    __syncthreads();
+    // flush: one box row per wave and pass, two instructions of 64 channels (256 contiguous bytes) each
+    float* base = (float*)gv.data + (int64_t)rb_b * gv.image_stride;
+#pragma unroll 1
+    for (int v = wave; v < d.rows; v += 4) {
+      int ix, iy, iz;
+      d.row_to_xyz(v, ix, iy, iz);
+      float* dst = base + adj_voxel(d, gv, ix, iy, iz);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int ch = 64 * h + lane;
+        const float val = box[v * kAdjC + (((ch >> 2) ^ (v & 31)) << 2) + (ch & 3)];
+        if (val != 0.f) atomicAdd(dst + ch, val * inv_s);
+      }
+    }
+  }
+};
+
+enum { ADJ_F16_PK = 0, ADJ_F16_F32 = 1, ADJ_SPLIT = 2 };      // k_scatter_vox_box<FORM>
+template <int FORM> struct AdjPolicy { using type = AdjF16<FORM>; };
+template <> struct AdjPolicy<ADJ_SPLIT> { using type = AdjSplit; };
+
+// grid = rows / 64, block = 256.  gv.data: the level's zeroed fp32 gradient; img16: its zeroed fp16 image (ADJ_F16_PK).
 // (243 registers, two workgroups per CU; held to 168 for three the compiler spills 300 B and the kernel takes 2.2x as long)
-template <int F32OUT>
+template <int FORM>
 __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, ListVoxLevel gv, int col_off,
                                                           _Float16* __restrict__ img16) {
-  using L = AdjLds;
-  constexpr int RB = L::kRowBytes;
-  constexpr int NT = kAdjC / 16;                                // 16-channel tiles
+  using P = typename AdjPolicy<FORM>::type;
+  using L = typename P::L;
+  static_assert(2 * P::kBufBytes <= P::kRegion, "the two staging buffers share the box's LDS");
+  constexpr int RB = kAdjRowBytes;
+  constexpr int NT = kAdjNT;
   __shared__ __attribute__((aligned(16))) char smem[L::total];
   AxisW* ptab = (AxisW*)(smem + L::ptab);
   RunBox* runs = (RunBox*)(smem + L::run);
@@ -74,56 +297,16 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
 
   // ---- 1a. waves 0..2: axis `wave` of the 64 points (as the forward); wave 3: the zero row ---------------------------
   if (wave < 3) {
-    const Pt p = load_point(sp.g, (int)row0 + lane);
-    const float c = wave == 0 ? p.x : (wave == 1 ? p.y : p.z);
-    const int S = wave == 0 ? W : (wave == 1 ? H : D);
-    const Axis a[3] = {axis_setup(c, S), axis_setup(c - kDisp, S), axis_setup(c + kDisp, S)};
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      AxisW e;
-      e.i0 = a[v].i0;
-      e.w0 = p.valid ? a[v].w0 : 0.f;
-      e.w1 = (p.valid && a[v].has1) ? a[v].w1 : 0.f;
-      ptab[(lane * 3 + wave) * 3 + v] = e;
-    }
-    pbox[lane * 4 + wave] = a[1].i0 | ((a[2].i0 + a[2].has1) << 8);
-    if (wave == 0) pbox[lane * 4 + 3] = p.valid ? p.b : -1;
+    box_point_records(sp.g, (int)row0 + lane, lane, wave, W, H, D, ptab, pbox);
   } else {
     *(unsigned*)(smem + L::zero + lane * 4) = 0u;
   }
   __syncthreads();
   // ---- 1b. wave 0: aligned power-of-two runs whose box fits -------------------------------------------------------------
-  if (wave == 0) {
-    const int4 pb = *(const int4*)(pbox + lane * 4);
-    const bool valid = pb.w >= 0;
-    SegBox sb;
-    sb.f0 = valid ? (unsigned)((pb.x & 255) | ((pb.y & 255) << 16)) : 0x7fff7fffu;
-    sb.f1 = valid ? (unsigned)((pb.z & 255) | ((255 - (pb.x >> 8)) << 16)) : 0x7fff7fffu;
-    sb.f2 = valid ? (unsigned)((255 - (pb.y >> 8)) | ((255 - (pb.z >> 8)) << 16)) : 0x7fff7fffu;
-    sb.bmin = valid ? pb.w : INT_MAX;
-    sb.nbmax = valid ? ~pb.w : INT_MAX;
-    int level = 0;
-    SegBox best = sb;
-#define LIST_SEG_STAGE(S)                                              \
-    seg_merge<S>(sb);                                                  \
-    if (level == S && seg_fits(sb, kAdjRows, INT_MAX)) { level = S + 1; best = sb; }
-    LIST_SEG_STAGE(0) LIST_SEG_STAGE(1) LIST_SEG_STAGE(2) LIST_SEG_STAGE(3) LIST_SEG_STAGE(4) LIST_SEG_STAGE(5)
-#undef LIST_SEG_STAGE
-    if ((lane & ((1 << level) - 1)) == 0) {
-      const bool any = best.bmin != INT_MAX;
-      const int lox = best.f0 & 0xffff, loy = best.f0 >> 16, loz = best.f1 & 0xffff;
-      const int hix = 255 - (int)(best.f1 >> 16), hiy = 255 - (int)(best.f2 & 0xffff), hiz = 255 - (int)(best.f2 >> 16);
-      RunBox rb;
-      rb.count = 1 << level;
-      rb.b = any ? best.bmin : 0;
-      rb.lo = any ? (lox | (loy << 8) | (loz << 16)) : 0;
-      rb.n = any ? ((hix - lox + 1) | ((hiy - loy + 1) << 8) | ((hiz - loz + 1) << 16)) : 0;
-      runs[lane] = rb;
-    }
-  }
+  if (wave == 0) box_cut_runs<kAdjRows, INT_MAX>(pbox, lane, runs);
   __syncthreads();
 
-  const unsigned short* __restrict__ dx = (const unsigned short*)sp.dx;
+  const typename P::Elem* __restrict__ dx = (const typename P::Elem*)sp.dx;
   const int q = lane >> 4, col = lane & 15;                    // MFMA lane roles: point of the K-step / box row of the tile
   const int tr_r = (lane >> 2) & 3, tr_p = lane & 3;           // transposed read: slot within the 4-slot block, 4-channel group
   // byte offset of channel tile t in a staged row, as this lane reads it: tile t = channels 32 (t >> 1) + 8 p + 4 (t & 1)
@@ -135,26 +318,27 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
   for (int t = 0; t < NT; ++t)
     aoff[t] = ((tr_p << 4) + (((t >> 1) << 6) | ((t & 1) << 3))) ^ ((tr_r << 6) | ((q & 1) << 3));
 
+  float inv_s = 0.f;
+  if (!P::kScaleInFlush) inv_s = sp.scale[1];
   int first = 0;
 #pragma unroll 1
   while (first < kAdjPts) {
     const RunBox rb = runs[first];
-    const int count = uni(rb.count), rb_b = uni(rb.b), rlo = uni(rb.lo), rn = uni(rb.n);
-    const int lox = rlo & 255, loy = (rlo >> 8) & 255, loz = rlo >> 16;
-    const int nx = rn & 255, ny = (rn >> 8) & 255, nz = rn >> 16;
-    const int rows = nx * ny * nz;
+    const int count = uni(rb.count), rb_b = uni(rb.b);
+    RunDims d = run_dims(uni(rb.lo), uni(rb.n));
+    const int rows = d.rows;
     if (rows == 0) { first += count; continue; }                // no valid point in the run (uniform)
+    d.set_inverses<false>();
     const int n_vt = (rows + 15) >> 4;                          // box-row tiles in use
-    const int inv_nx = (65536 + nx - 1) / nx, inv_ny = (65536 + ny - 1) / ny;
     // this lane's box rows (tiles wave, wave + 4) as absolute voxel coordinates; a row beyond the box matches nothing
     int vx[2], vy[2], vz[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int v = 16 * (wave + 4 * i) + col;
-      const int yz = (v * inv_nx) >> 16, ix = v - yz * nx;
-      const int iz = (yz * inv_ny) >> 16, iy = yz - iz * ny;
+      int ix, iy, iz;
+      d.row_to_xyz(v, ix, iy, iz);
       const bool in = v < rows;
-      vx[i] = in ? lox + ix : -4; vy[i] = in ? loy + iy : -4; vz[i] = in ? loz + iz : -4;
+      vx[i] = in ? d.lox + ix : -4; vy[i] = in ? d.loy + iy : -4; vz[i] = in ? d.loz + iz : -4;
     }
     const bool own0 = wave < n_vt, own1 = wave + 4 < n_vt;      // (uniform)
     f32x4v acc[2][NT];
@@ -163,30 +347,30 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
 #pragma unroll
       for (int t = 0; t < NT; ++t) acc[i][t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
 
-    // staging of chunk ci: rows (point, slot j < 7) x 16 chunks of 16 B = 896 pieces, 3.5 per thread
+    // staging of chunk ci: rows (point, slot j < 7) x 16 pieces of 8 channels = 896 pieces, 3.5 per thread; physical
+    // position chunk ^ (j & 3) << 2, 8-B halfs swapped for odd points.  The next chunk's pieces are requested a chunk ahead
     const int nchunks = (count + kAdjChunkPts - 1) / kAdjChunkPts;
-    uint4 sv[4];
+    typename P::Piece sv[4];
     auto stage_load = [&](int ci) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = tid + 256 * e;
         const int r = i >> 4, chunk = i & 15;
         const int pl = r / LIST_N_STENCIL, j = r - pl * LIST_N_STENCIL;
-        sv[e] = make_uint4(0u, 0u, 0u, 0u);
-        if (i < L::kStageRows * 16 && ci * kAdjChunkPts + pl < count)
-          sv[e] = *(const uint4*)(dx + (row0 + first + ci * kAdjChunkPts + pl) * sp.g.Kp + col_off + j * kAdjC + chunk * 8);
+        sv[e] = P::no_piece();
+        if (i < kAdjStageRows * 16 && ci * kAdjChunkPts + pl < count)
+          sv[e] = P::load_piece(dx + (row0 + first + ci * kAdjChunkPts + pl) * sp.g.Kp + col_off + j * kAdjC + chunk * 8);
       }
     };
     auto stage_store = [&](int ci) {
-      char* buf = smem + L::stage + (ci & 1) * L::stage_bytes;
+      char* buf = smem + L::stage + (ci & 1) * P::kBufBytes;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = tid + 256 * e;
-        if (i >= L::kStageRows * 16) continue;
+        if (i >= kAdjStageRows * 16) continue;
         const int r = i >> 4, chunk = i & 15;
         const int pl = r / LIST_N_STENCIL, j = r - pl * LIST_N_STENCIL;
-        const uint4 w = (pl & 1) ? make_uint4(sv[e].z, sv[e].w, sv[e].x, sv[e].y) : sv[e];
-        *(uint4*)(buf + r * RB + ((chunk ^ ((j & 3) << 2)) << 4)) = w;
+        P::store_piece(buf, r * RB + ((chunk ^ ((j & 3) << 2)) << 4), pl & 1, sv[e]);
       }
     };
     stage_load(0);
@@ -195,7 +379,7 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
       stage_store(ci);
       __syncthreads();                 // (one barrier per chunk: the other buffer was last read before the previous barrier)
       if (ci + 1 < nchunks) stage_load(ci + 1);
-      const char* buf = smem + L::stage + (ci & 1) * L::stage_bytes;
+      const char* buf = smem + L::stage + (ci & 1) * P::kBufBytes;
       // (the MFMAs left out, staging and barriers only: 16^3 level 0.239 -> 0.125 ms, 8^3 0.118 -> 0.070)
 #pragma unroll 1
       for (int ks = 0; ks < kAdjChunkPts / 4; ++ks) {
@@ -205,16 +389,13 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
         const bool live = pl < count;
         const int pt = first + (live ? pl : 0);
         // A: slots 0..3 and 4..7 of this lane's point; slot 7 and points beyond the run read the zero row
+        const bool live_hi = live && tr_r < 3;
         const char* a_lo = live ? buf + (plc * LIST_N_STENCIL + tr_r) * RB : smem + L::zero;
-        const char* a_hi = (live && tr_r < 3) ? buf + (plc * LIST_N_STENCIL + 4 + tr_r) * RB : smem + L::zero;
-        s16x4 a0[NT], a1[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          a0[t] = tr_read16(a_lo + aoff[t]);
-          a1[t] = tr_read16(a_hi + aoff[t]);
-        }
+        const char* a_hi = live_hi ? buf + (plc * LIST_N_STENCIL + 4 + tr_r) * RB : smem + L::zero;
+        const typename P::AFrag a = P::a_frags(a_lo, a_hi, live, live_hi, aoff);
         // B: the 7 weights of (point, slot) at this lane's voxel, per owned tile (the factor of an axis is the record's
-        // w0 where the voxel is the base tap, w1 where it is the next one, 0 elsewhere)
+        // w0 where the voxel is the base tap, w1 where it is the next one, 0 elsewhere), split hi + lo in the operand's
+        // 16-bit format
         const AxisW* rec = ptab + pt * 9;
         float hx[2][3], hy[2][3], hz[2][3];
 #pragma unroll
@@ -228,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
             hz[i][v] = dzv == 0 ? fz.w0 : (dzv == 1 ? fz.w1 : 0.f);
           }
         }
-        f16x8 bhi[2], blo[2];
+        uint4 bhi[2], blo[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           if (i == 0 ? !own0 : !own1) continue;
@@ -238,104 +419,43 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
           unsigned hi[4], lo[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            hi[e] = pk_h2(w[2 * e], w[2 * e + 1]);
-            lo[e] = pk_h2(w[2 * e] - h2f((unsigned short)(hi[e] & 0xffffu)), w[2 * e + 1] - h2f((unsigned short)(hi[e] >> 16)));
+            hi[e] = P::pk2(w[2 * e], w[2 * e + 1]);
+            lo[e] = P::pk2(w[2 * e] - P::up((unsigned short)(hi[e] & 0xffffu)), w[2 * e + 1] - P::up((unsigned short)(hi[e] >> 16)));
           }
-          bhi[i] = __builtin_bit_cast(f16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
-          blo[i] = __builtin_bit_cast(f16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
+          bhi[i] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+          blo[i] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          if (i == 0 ? !own0 : !own1) continue;
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            const f16x8 a = __builtin_bit_cast(f16x8, (s16x8){a0[t][0], a0[t][1], a0[t][2], a0[t][3], a1[t][0], a1[t][1], a1[t][2], a1[t][3]});
-            acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bhi[i], acc[i][t], 0, 0, 0);
-          }
-          // the lo plane of the weights: rounding them to fp16 alone would save 16^3 level 0.253 -> 0.230 ms -- not
-          // worth the exactness
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            const f16x8 a = __builtin_bit_cast(f16x8, (s16x8){a0[t][0], a0[t][1], a0[t][2], a0[t][3], a1[t][0], a1[t][1], a1[t][2], a1[t][3]});
-            acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, blo[i], acc[i][t], 0, 0, 0);
-          }
-        }
+        P::mma(a, aoff, bhi, blo, own0, own1, acc);
       }
     }
-    if (F32OUT) {
-      // D: column = box row (lane & 15), rows 4 q + reg of tile t = channels 32 (t >> 1) + 8 q + 4 (t & 1) + reg
-      const float inv_s = sp.scale[1];
-      float* base = (float*)gv.data + (int64_t)rb_b * gv.image_stride;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (i == 0 ? !own0 : !own1) continue;
-        const int v = 16 * (wave + 4 * i) + col;
-        if (v >= rows) continue;
-        const int yz = (v * inv_nx) >> 16, ix = v - yz * nx;
-        const int iz = (yz * inv_ny) >> 16, iy = yz - iz * ny;
-        float* dst = base + ((int64_t)((loz + iz) * H + (loy + iy)) * W + (lox + ix)) * kAdjC;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float val = acc[i][t][e];
-            if (val != 0.f) atomicAdd(dst + 32 * (t >> 1) + 8 * q + 4 * (t & 1) + e, val * inv_s);
-          }
-      }
-      first += count;
-      if (first < kAdjPts) __syncthreads();                     // the next run stages over the buffers
-      continue;
-    }
-    __syncthreads();                   // every wave is done with the staging buffers: the box takes their place
-    // D: column = box row (lane & 15), rows 4 q + reg of tile t = channels 32 (t >> 1) + 8 q + 4 (t & 1) + reg -> 16-B
-    // pieces of 8 consecutive channels, chunk XOR (row & 15) (the 16 rows of a tile land on distinct banks)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (i == 0 ? !own0 : !own1) continue;
-      const int v = 16 * (wave + 4 * i) + col;
-#pragma unroll
-      for (int u = 0; u < NT / 2; ++u) {
-        const f32x4v c0 = acc[i][2 * u], c1 = acc[i][2 * u + 1];
-        const uint2 lo = half4_inrange(make_float4(c0[0] * kAdjPkScale, c0[1] * kAdjPkScale, c0[2] * kAdjPkScale, c0[3] * kAdjPkScale));
-        const uint2 hi = half4_inrange(make_float4(c1[0] * kAdjPkScale, c1[1] * kAdjPkScale, c1[2] * kAdjPkScale, c1[3] * kAdjPkScale));
-        *(uint4*)(smem + L::stage + v * RB + (((4 * u + q) ^ col) << 4)) = make_uint4(lo.x, lo.y, hi.x, hi.y);
-      }
-    }
-    __syncthreads();
-    // flush: lanes over channel pairs, one box row per wave and pass -- 256 contiguous bytes per atomic instruction
-    // (its share: 16^3 level 0.239 -> 0.154 ms, 8^3 0.118 -> 0.104 without it)
-    {
-      typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-      _Float16* base16 = img16 + (int64_t)rb_b * gv.image_stride;
-      // one box row per wave and pass (its voxel address is scalar arithmetic), lane = channel pair 2 lane, 2 lane + 1
-#pragma unroll 1
-      for (int v = wave; v < rows; v += 4) {
-        const int yz = (v * inv_nx) >> 16, ix = v - yz * nx;           // (exact for v < 256: the forward's box copy)
-        const int iz = (yz * inv_ny) >> 16, iy = yz - iz * ny;
-        const unsigned bits = *(const unsigned*)(smem + L::stage + v * RB + ((((lane >> 2) ^ (v & 15)) << 4) | ((lane & 3) << 2)));
-        if ((bits & 0x7fff7fffu) == 0u) continue;
-        __builtin_amdgcn_global_atomic_fadd_v2f16(
-            (__attribute__((address_space(1))) half2v*)(base16 + ((int64_t)((loz + iz) * H + (loy + iy)) * W + (lox + ix)) * kAdjC + 2 * lane),
-            __builtin_bit_cast(half2v, bits));
-      }
-    }
+    if (P::kScaleInFlush) inv_s = sp.scale[1];
+    P::flush(smem, acc, d, rb_b, wave, lane, own0, own1, gv, inv_s, img16);
     first += count;
-    if (first < kAdjPts) __syncthreads();                       // the next run stages over the box
+    if (first < kAdjPts) __syncthreads();                       // the next run stages over the buffers / the box
   }
 }
 
-// a window level (stencil shorter than a voxel), fp16 dX, 128 channels, image scaled by `pk_scale`
+// a window level (stencil shorter than a voxel), 128 channels; fp16 dX: the packed-half flush into an fp16 image scaled
+// by kAdjPkScale (form ADJ_F16_PK) or the diagnostic fp32 flush (ADJ_F16_F32); fp32 dX: ADJ_SPLIT
 bool scatter_box_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, float pk_scale) {
-  if (!sp.dx_f16 || gv.C != kAdjC || pk_scale != kAdjPkScale) return false;
-  if ((col_off % 8) != 0 || (sp.g.Kp % 8) != 0 || (gv.image_stride % 2) != 0) return false;
+  if (gv.C != kAdjC) return false;
+  if (sp.dx_f16) {
+    if (pk_scale != kAdjPkScale) return false;
+    if ((col_off % 8) != 0 || (sp.g.Kp % 8) != 0 || (gv.image_stride % 2) != 0) return false;
+  } else {
+    if ((col_off % 4) != 0 || (sp.g.Kp % 4) != 0) return false;
+  }
   if (gv.W > 255 || gv.H > 255 || gv.D > 255) return false;   // 8-bit coordinates in the run records
   return (sp.g.rows % kAdjPts) == 0;
 }
 
+// img16: the level's zeroed fp16 image (fp16 dX), or null: fp32 atomics into gv.data
 hipError_t launch_scatter_vox_box(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, _Float16* img16,
                                   hipStream_t s) {
-  if (img16) hipLaunchKernelGGL(k_scatter_vox_box<0>, dim3((unsigned)(sp.g.rows / kAdjPts)), dim3(256), 0, s, sp, gv, col_off, img16);
-  else hipLaunchKernelGGL(k_scatter_vox_box<1>, dim3((unsigned)(sp.g.rows / kAdjPts)), dim3(256), 0, s, sp, gv, col_off, img16);
+  const dim3 grid((unsigned)(sp.g.rows / kAdjPts));
+  if (!sp.dx_f16) hipLaunchKernelGGL(k_scatter_vox_box<ADJ_SPLIT>, grid, dim3(256), 0, s, sp, gv, col_off, (_Float16*)nullptr);
+  else if (img16) hipLaunchKernelGGL(k_scatter_vox_box<ADJ_F16_PK>, grid, dim3(256), 0, s, sp, gv, col_off, img16);
+  else hipLaunchKernelGGL(k_scatter_vox_box<ADJ_F16_F32>, grid, dim3(256), 0, s, sp, gv, col_off, img16);
   return hipGetLastError();
 }
 

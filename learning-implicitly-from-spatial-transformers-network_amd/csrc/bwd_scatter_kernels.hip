@@ -731,38 +731,40 @@ static bool scatter_f32_diagnostic() {
   return on;
 }
 
+// stencil displacement in voxels of the level's longest axis; a window level: wide channels and a stencil shorter than
+// a voxel (the LDS-window kernel or the matrix-core adjoint)
+static float stencil_reach(const ListVoxLevel& gv) {
+  const int big = gv.W > gv.H ? (gv.W > gv.D ? gv.W : gv.D) : (gv.H > gv.D ? gv.H : gv.D);
+  return kDisp * 0.5f * (float)(big - 1);
+}
+static bool is_window_level(const ListVoxLevel& gv) { return gv.C >= 64 && stencil_reach(gv) < 0.99f; }
+
+template <int C, int kWinFloats>
+static void launch_scatter_vox_win(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s, _Float16* img16) {
+  constexpr int T = C >= 128 ? C : 128;
+  const dim3 grid((unsigned)(sp.g.rows / kScatterRows));
+  if (sp.dx_f16) hipLaunchKernelGGL((k_scatter_vox_win<C, 1, kWinFloats>), grid, dim3(T), 0, s, sp, gv, col_off, img16);
+  else hipLaunchKernelGGL((k_scatter_vox_win<C, 0, kWinFloats>), grid, dim3(T), 0, s, sp, gv, col_off, (_Float16*)nullptr);
+}
+
 template <int C>
 static hipError_t scatter_level(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s,
                                 _Float16* img16 = nullptr) {
-  const dim3 grid((unsigned)(sp.g.rows / kScatterRows));
-  const int big = gv.W > gv.H ? (gv.W > gv.D ? gv.W : gv.D) : (gv.H > gv.D ? gv.H : gv.D);
-  const float reach = kDisp * 0.5f * (float)(big - 1);          // stencil displacement in voxels
   if constexpr (C >= 64) {
-    if (reach < 0.99f) {
-      constexpr int T = C >= 128 ? C : 128;
-      if (reach < 0.34f) {          // 8^3: small boxes, four workgroups per CU
-        // fp16, 128 channels: on the matrix cores (k_scatter_vox_box) -- alone 0.28 -> 0.12 ms; beside the other streams of
-        // the forked backward the VALU kernel is the better neighbour (2 waves of 199 registers per workgroup against 4 of
-        // 243: step +0.05 ms with the matrix-core form), so forked calls keep it unless LIST_SCATTER_BOX=2
-        const int box_mode = scatter_box_mode();
-        const bool box8 = box_mode < 0 ? !sp.forked : (box_mode == 1 || box_mode == 2);
-        if (box8 && (img16 || scatter_f32_diagnostic()) && scatter_box_eligible(sp, gv, col_off, kWinPkScale))
-          return launch_scatter_vox_box(sp, gv, col_off, img16, s);
-        if (box8 && !img16 && scatter_box_split_eligible(sp, gv, col_off))       // fp32 dX (bf16x3, bf16): bf16 hi + lo operands
-          return launch_scatter_vox_box_split(sp, gv, col_off, s);
-        if (sp.dx_f16) hipLaunchKernelGGL((k_scatter_vox_win<C, 1, 9216>), grid, dim3(T), 0, s, sp, gv, col_off, img16);
-        else hipLaunchKernelGGL((k_scatter_vox_win<C, 0, 9216>), grid, dim3(T), 0, s, sp, gv, col_off, (_Float16*)nullptr);
-      } else {
-        // 16^3: the same kernel with runs of <= 128 box rows: alone 0.52 -> 0.24 ms, forked step 6.63 -> 6.29 ms
-        const int box_mode = scatter_box_mode();
-        const bool box16 = box_mode < 0 || box_mode == 2 || box_mode == 3;
-        if (box16 && (img16 || scatter_f32_diagnostic()) && scatter_box_eligible(sp, gv, col_off, kWinPkScale))
-          return launch_scatter_vox_box(sp, gv, col_off, img16, s);
-        if (box16 && !img16 && scatter_box_split_eligible(sp, gv, col_off))
-          return launch_scatter_vox_box_split(sp, gv, col_off, s);
-        if (sp.dx_f16) hipLaunchKernelGGL((k_scatter_vox_win<C, 1, 18432>), grid, dim3(T), 0, s, sp, gv, col_off, img16);
-        else hipLaunchKernelGGL((k_scatter_vox_win<C, 0, 18432>), grid, dim3(T), 0, s, sp, gv, col_off, (_Float16*)nullptr);
-      }
+    if (is_window_level(gv)) {
+      const bool small_box = stencil_reach(gv) < 0.34f;         // 8^3: small boxes, four window workgroups per CU
+      // 128 channels: on the matrix cores (k_scatter_vox_box).  16^3: alone 0.52 -> 0.24 ms, forked step 6.63 -> 6.29 ms.
+      // 8^3: alone 0.28 -> 0.12 ms; beside the other streams of the forked backward the VALU kernel is the better
+      // neighbour (2 waves of 199 registers per workgroup against 4 of 243: step +0.05 ms with the matrix-core form), so
+      // forked calls keep it unless LIST_SCATTER_BOX=2
+      const int box_mode = scatter_box_mode();
+      const bool box = small_box ? (box_mode < 0 ? !sp.forked : (box_mode == 1 || box_mode == 2))
+                                 : (box_mode < 0 || box_mode == 2 || box_mode == 3);
+      // fp16 dX: into the fp16 image, or (diagnostic) fp32 atomics; fp32 dX (bf16x3, bf16): bf16 hi + lo operands
+      if (box && (sp.dx_f16 ? (img16 || scatter_f32_diagnostic()) : !img16) && scatter_box_eligible(sp, gv, col_off, kWinPkScale))
+        return launch_scatter_vox_box(sp, gv, col_off, img16, s);
+      if (small_box) launch_scatter_vox_win<C, 9216>(sp, gv, col_off, s, img16);
+      else launch_scatter_vox_win<C, 18432>(sp, gv, col_off, s, img16);
       return hipGetLastError();
     }
   }
@@ -771,6 +773,22 @@ static hipError_t scatter_level(const ScatterParams& sp, const ListVoxLevel& gv,
   const dim3 pgrid((unsigned)(nblocks < cap ? nblocks : cap));
   if (sp.dx_f16) hipLaunchKernelGGL((k_scatter_vox<C, 1>), pgrid, dim3(256), 0, s, sp, gv, col_off, nblocks);
   else hipLaunchKernelGGL((k_scatter_vox<C, 0>), pgrid, dim3(256), 0, s, sp, gv, col_off, nblocks);
+  return hipGetLastError();
+}
+
+// packed-half atomics: zero the level's fp16 image, run `scatter` into it, then one pass to the fp32 gradient
+// (k_h16_to_grad: 1 / s times `unscale`, the inverse of the image's own scale)
+template <class Scatter>
+static hipError_t scatter_via_h16(const ScatterParams& sp, const ListVoxLevel& gv, _Float16* img16, size_t n_elem,
+                                  float unscale, hipStream_t s, Scatter scatter) {
+  hipError_t e = hipMemsetAsync(img16, 0, n_elem * 2, s);
+  if (e != hipSuccess) return e;
+  e = scatter(img16);
+  if (e != hipSuccess) return e;
+  const int64_t n8 = (int64_t)(n_elem / 8);
+  const int64_t cb = (n8 + 255) / 256;
+  hipLaunchKernelGGL(k_h16_to_grad, dim3((unsigned)(cb < 8192 ? cb : 8192)), dim3(256), 0, s,
+                     (const _Float16*)img16, (float*)gv.data, n8, sp.scale, unscale);
   return hipGetLastError();
 }
 
@@ -786,8 +804,7 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
     hipError_t e = hipSuccess;
     // voxel-side gather where the samples are dense enough: at least kVoxGatherMinDensity samples per cell
     const int64_t n_vox = (int64_t)B * gv.D * gv.H * gv.W;
-    const int big = gv.W > gv.H ? (gv.W > gv.D ? gv.W : gv.D) : (gv.H > gv.D ? gv.H : gv.D);
-    const bool window_level = gv.C >= 64 && kDisp * 0.5f * (float)(big - 1) < 0.99f;
+    const bool window_level = is_window_level(gv);
     const bool dense = vb.mode == 2 || (vb.mode == 0 && !window_level &&
                                          (double)sp.g.n_valid * LIST_N_STENCIL >= kVoxGatherMinDensity * (double)n_vox);
     if (vb.bins && dense && n_vox <= kVoxGatherMaxBins && (gv.C == 16 || gv.C == 32 || gv.C == 64 ||
@@ -818,20 +835,16 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
       const size_t n_elem = (size_t)B * gv.image_stride;
       if (sp.dx_f16 && vb.mode == 0 && !window_level && (gv.C == 32 || gv.C == 64) && vb.h16 &&
           n_elem * 2 <= vb.h16_bytes && n_elem % 8 == 0 && gv.image_stride == (int64_t)gv.D * gv.H * gv.W * gv.C) {
-        e = hipMemsetAsync(vb.h16, 0, n_elem * 2, s);
-        if (e != hipSuccess) return e;
-        const int nblocks = sp.g.rows / kScatterRows;
-        const int cap = sp.forked ? kDirectGridForked : kDirectGrid;
-        const dim3 pgrid((unsigned)(nblocks < cap ? nblocks : cap));
-        if (gv.C == 32)
-          hipLaunchKernelGGL(k_scatter_vox_h2<32>, pgrid, dim3(256), 0, s, sp, gv, L.vox_off[l], nblocks, (_Float16*)vb.h16);
-        else
-          hipLaunchKernelGGL(k_scatter_vox_h2<64>, pgrid, dim3(256), 0, s, sp, gv, L.vox_off[l], nblocks, (_Float16*)vb.h16);
-        const int64_t n8 = (int64_t)(n_elem / 8);
-        const int64_t cb = (n8 + 255) / 256;
-        hipLaunchKernelGGL(k_h16_to_grad, dim3((unsigned)(cb < 8192 ? cb : 8192)), dim3(256), 0, s,
-                           (const _Float16*)vb.h16, (float*)gv.data, n8, sp.scale, 1.f);
-        e = hipGetLastError();
+        e = scatter_via_h16(sp, gv, (_Float16*)vb.h16, n_elem, 1.f, s, [&](_Float16* img) {
+          const int nblocks = sp.g.rows / kScatterRows;
+          const int cap = sp.forked ? kDirectGridForked : kDirectGrid;
+          const dim3 pgrid((unsigned)(nblocks < cap ? nblocks : cap));
+          if (gv.C == 32)
+            hipLaunchKernelGGL(k_scatter_vox_h2<32>, pgrid, dim3(256), 0, s, sp, gv, L.vox_off[l], nblocks, img);
+          else
+            hipLaunchKernelGGL(k_scatter_vox_h2<64>, pgrid, dim3(256), 0, s, sp, gv, L.vox_off[l], nblocks, img);
+          return hipSuccess;
+        });
         if (e != hipSuccess) return e;
         continue;
       }
@@ -845,19 +858,13 @@ hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, cons
       if (n_elem * 2 <= slot && n_elem % 8 == 0 && n_win_pk < 2 &&
           gv.image_stride == (int64_t)gv.D * gv.H * gv.W * gv.C) {
         ++n_win_pk;
-        e = hipMemsetAsync(img, 0, n_elem * 2, s);
-        if (e != hipSuccess) return e;
-        switch (gv.C) {
-          case 64: e = scatter_level<64>(sp, gv, L.vox_off[l], s, (_Float16*)img); break;
-          case 128: e = scatter_level<128>(sp, gv, L.vox_off[l], s, (_Float16*)img); break;
-          default: e = scatter_level<256>(sp, gv, L.vox_off[l], s, (_Float16*)img); break;
-        }
-        if (e != hipSuccess) return e;
-        const int64_t n8 = (int64_t)(n_elem / 8);
-        const int64_t cb = (n8 + 255) / 256;
-        hipLaunchKernelGGL(k_h16_to_grad, dim3((unsigned)(cb < 8192 ? cb : 8192)), dim3(256), 0, s,
-                           (const _Float16*)img, (float*)gv.data, n8, sp.scale, 1.f / kWinPkScale);
-        e = hipGetLastError();
+        e = scatter_via_h16(sp, gv, (_Float16*)img, n_elem, 1.f / kWinPkScale, s, [&](_Float16* img16) {
+          switch (gv.C) {
+            case 64: return scatter_level<64>(sp, gv, L.vox_off[l], s, img16);
+            case 128: return scatter_level<128>(sp, gv, L.vox_off[l], s, img16);
+            default: return scatter_level<256>(sp, gv, L.vox_off[l], s, img16);
+          }
+        });
         if (e != hipSuccess) return e;
         continue;
       }

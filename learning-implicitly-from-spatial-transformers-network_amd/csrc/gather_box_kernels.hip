@@ -78,56 +78,16 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
   const int64_t row0 = (int64_t)blk * kBoxPts;
   const int W = lv.W, H = lv.H, D = lv.D;
 
-  // ---- 1a. waves 0..2: axis `wave` of the 64 points -- weight records of the centre / -d / +d coordinate -----------
+  // ---- 1a. waves 0..2: axis `wave` of the 64 points -- weight records of the centre / -d / +d coordinate; wave 3: the
+  //          key counters -----------------------------------------------------------------------------------------------
   if (wave < 3) {
-    const Pt p = load_point(g, (int)row0 + lane);
-    const float c = wave == 0 ? p.x : (wave == 1 ? p.y : p.z);
-    const int S = wave == 0 ? W : (wave == 1 ? H : D);
-    const Axis a[3] = {axis_setup(c, S), axis_setup(c - kDisp, S), axis_setup(c + kDisp, S)};
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      AxisW e;
-      e.i0 = a[v].i0;
-      e.w0 = p.valid ? a[v].w0 : 0.f;
-      e.w1 = (p.valid && a[v].has1) ? a[v].w1 : 0.f;
-      ptab[(lane * 3 + wave) * 3 + v] = e;
-    }
-    pbox[lane * 4 + wave] = a[1].i0 | ((a[2].i0 + a[2].has1) << 8);
-    if (wave == 0) pbox[lane * 4 + 3] = p.valid ? p.b : -1;
+    box_point_records(g, (int)row0 + lane, lane, wave, W, H, D, ptab, pbox);
   } else {
     for (int k = lane; k < kBoxMaxKeys; k += 64) keyinfo[k] = 0;
   }
   __syncthreads();
   // ---- 1b. wave 0: aligned power-of-two runs whose box fits (segment tree over the tap ranges) ----------------------
-  if (wave == 0) {
-    const int4 pb = *(const int4*)(pbox + lane * 4);
-    const bool valid = pb.w >= 0;
-    SegBox sb;
-    sb.f0 = valid ? (unsigned)((pb.x & 255) | ((pb.y & 255) << 16)) : 0x7fff7fffu;
-    sb.f1 = valid ? (unsigned)((pb.z & 255) | ((255 - (pb.x >> 8)) << 16)) : 0x7fff7fffu;
-    sb.f2 = valid ? (unsigned)((255 - (pb.y >> 8)) | ((255 - (pb.z >> 8)) << 16)) : 0x7fff7fffu;
-    sb.bmin = valid ? pb.w : INT_MAX;
-    sb.nbmax = valid ? ~pb.w : INT_MAX;
-    // a segment that fits contains only segments that fit: the largest fitting level is the same for all its lanes
-    int level = 0;
-    SegBox best = sb;
-#define LIST_SEG_STAGE(S)                                              \
-    seg_merge<S>(sb);                                                  \
-    if (level == S && seg_fits(sb, MAXROWS, kBoxMaxKeys)) { level = S + 1; best = sb; }
-    LIST_SEG_STAGE(0) LIST_SEG_STAGE(1) LIST_SEG_STAGE(2) LIST_SEG_STAGE(3) LIST_SEG_STAGE(4) LIST_SEG_STAGE(5)
-#undef LIST_SEG_STAGE
-    if ((lane & ((1 << level) - 1)) == 0) {
-      const bool any = best.bmin != INT_MAX;
-      const int lox = best.f0 & 0xffff, loy = best.f0 >> 16, loz = best.f1 & 0xffff;
-      const int hix = 255 - (int)(best.f1 >> 16), hiy = 255 - (int)(best.f2 & 0xffff), hiz = 255 - (int)(best.f2 >> 16);
-      RunBox rb;
-      rb.count = 1 << level;
-      rb.b = any ? best.bmin : 0;
-      rb.lo = any ? (lox | (loy << 8) | (loz << 16)) : 0;
-      rb.n = any ? ((hix - lox + 1) | ((hiy - loy + 1) << 8) | ((hiz - loz + 1) << 16)) : 0;
-      runs[lane] = rb;
-    }
-  }
+  if (wave == 0) box_cut_runs<MAXROWS, kBoxMaxKeys>(pbox, lane, runs);
   __syncthreads();
 
   const unsigned short* __restrict__ vsrc = (const unsigned short*)lv.data;
@@ -139,15 +99,14 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
 #pragma unroll 1
   while (first < kBoxPts) {
     const RunBox rb = runs[first];
-    const int count = uni(rb.count), rb_b = uni(rb.b), rlo = uni(rb.lo), rn = uni(rb.n);
-    const int lox = rlo & 255, loy = (rlo >> 8) & 255, loz = rlo >> 16;
-    const int nx = rn & 255, ny = (rn >> 8) & 255, nz = rn >> 16;
-    const int rows = nx * ny * nz;
+    const int count = uni(rb.count), rb_b = uni(rb.b);
+    RunDims d = run_dims(uni(rb.lo), uni(rb.n));
+    d.set_inverses<true>();                                     // (a run without a valid point still zeroes padding rows)
+    const int lox = d.lox, loy = d.loy, loz = d.loz, nx = d.nx, ny = d.ny, nz = d.nz, rows = d.rows;
     const int fw0 = lox >> 2;
     const int nfw = rows ? ((lox + nx - 1) >> 2) - fw0 + 1 : 0;
     const int nkeys = nfw * ny * nz;
-    const int inv_nx = (65536 + nx - 1) / (nx > 0 ? nx : 1), inv_ny = (65536 + ny - 1) / (ny > 0 ? ny : 1);
-    const int inv_nz = (65536 + nz - 1) / (nz > 0 ? nz : 1);
+    const int inv_ny = d.inv_ny, inv_nz = box_inv<true>(nz);    // window key -> (y0, z0, window)
 
     // ---- 2a. the voxel box: requested now (16-B chunks, lanes over channels: coalesced 256-B rows), landed in LDS
     //          behind the bucketing below ---------------------------------------------------------------------------
@@ -161,8 +120,8 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
         const int r = i * RPP + tid / CH;
         bdst[i] = -1;
         if (r < rows) {
-          const int yz = (r * inv_nx) >> 16, ix = r - yz * nx;
-          const int iz = (yz * inv_ny) >> 16, iy = yz - iz * ny;
+          int ix, iy, iz;
+          d.row_to_xyz(r, ix, iy, iz);
           const int64_t src = ibase + ((int64_t)((loz + iz) * H + (loy + iy)) * W + (lox + ix)) * C + chunk * 8;
           bv[i] = *(const uint4*)(vsrc + src);
           // physical position: chunk ^ ((ix & 3) << 2), 8-B halfs swapped in odd (iy + iz) cells: the 32 lanes of a

@@ -44,6 +44,7 @@ __device__ __forceinline__ void x_store(const V& v, V* p) {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4v;      // MFMA 16x16 accumulator
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
@@ -525,11 +526,9 @@ constexpr double kVoxGatherMinDensity = 2.0;         // samples per cell
 // levels (packed-half atomics), or null
 struct VoxGatherBuffers { int* keys; int* bins; int* sums; void* recs; int mode; void* h16; size_t h16_bytes; void* h16w; size_t h16w_bytes; };
 // the three adjoint forms may run on different streams (gather / direct atomics / LDS windows)
-// matrix-core adjoint of an 8^3-class level (bwd_box_kernels.hip); pk_scale: the scale of the level's fp16 image
+// matrix-core adjoint of a window level (bwd_box_kernels.hip).  fp16 dX: packed-half flush into img16, the level's zeroed
+// fp16 image at scale pk_scale, or (img16 null, diagnostic) fp32 atomics; fp32 dX: bf16 hi + lo operands, fp32 flush
 bool scatter_box_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, float pk_scale);
-// ... and for the formats whose dX is fp32 (bwd_box_split_kernels.hip: bf16 hi + lo operands, fp32 flush)
-bool scatter_box_split_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off);
-hipError_t launch_scatter_vox_box_split(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s);
 hipError_t launch_scatter_vox_box(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, _Float16* img16,
                                   hipStream_t s);
 struct ScatterStreams { hipStream_t gather, direct, window, window2; };

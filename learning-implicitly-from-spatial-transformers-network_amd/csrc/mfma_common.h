@@ -46,8 +46,6 @@ __device__ __forceinline__ void store8_planes(unsigned short* __restrict__ hi, u
 }
 
 
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
 template <int FP16>
 __device__ __forceinline__ f32x4v mfma16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
   if (FP16)

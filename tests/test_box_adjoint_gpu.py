@@ -1,4 +1,4 @@
-"""GPU: the matrix-core adjoint of the coarse voxel levels (k_scatter_vox_box / k_scatter_vox_box_split, csrc/bwd_box*_kernels.hip; the reference's autograd of
+"""GPU: the matrix-core adjoint of the coarse voxel levels (k_scatter_vox_box, csrc/bwd_box_kernels.hip; the reference's autograd of
 network/modules.py:256-265 for the 16^3 and 8^3 x 128-channel levels, fp16 operands) against the LDS-window kernel it replaces.
 
 Both consume the SAME dX (everything before the voxel adjoint is deterministic) and flush packed halfs into the same fp16 image, so they
@@ -95,7 +95,7 @@ def test_matrix_core_adjoint_equals_the_window_kernel_when_both_flush_fp32(tmp_p
 
 @pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
 def test_split_operand_adjoint_equals_the_window_kernel_to_its_products_grade(tmp_path, precision):
-    """The formats whose dX is fp32 (k_scatter_vox_box_split, bwd_box_split_kernels.hip): both kernels add fp32 sums into the fp32
+    """The formats whose dX is fp32 (k_scatter_vox_box<ADJ_SPLIT>, bwd_box_kernels.hip): both kernels add fp32 sums into the fp32
     gradient; the window kernel multiplies in fp32, the matrix-core kernel takes bf16 hi + lo of both operands (three products,
     16 mantissa bits each way -- the grade of the forward's bf16x3 GEMMs): 3 - 6e-6 of a level's largest entry measured, against
     2e-7 for the window kernel twice and 2e-4 for the bf16x3 path's stated bound."""
