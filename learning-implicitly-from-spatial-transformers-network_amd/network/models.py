@@ -7,6 +7,15 @@ import torch.nn as nn
 from . import modules as M
 
 
+def _coarse_stage_of(config):
+    """"hip": the stage between the image encoders and the 3-D encoder runs in HIP (coarse.py) for tensors on a HIP
+    device; eval mode and no gradients only (a call in train() raises, it never falls back)."""
+    kind = getattr(config, "coarse_stage", "torch")
+    if kind not in ("torch", "hip"):
+        raise ValueError(f"coarse_stage = {kind!r}: 'torch' or 'hip'")
+    return kind
+
+
 class CoarseNet(nn.Module):
     """RGB image -> coarse point cloud [B, prod(point_degree), 3]."""
 
@@ -15,9 +24,13 @@ class CoarseNet(nn.Module):
         self.image_encoder = M.ResEncoder()
         self.point_decoder = M.TreeGraphDecoder(config.train_batch_size, config.point_feat,
                                                 config.point_degree, 10)
+        self.coarse_stage = _coarse_stage_of(config)
 
     def forward(self, rgba):
         featvecs, _ = self.image_encoder(rgba)
+        if self.coarse_stage == "hip" and featvecs.is_cuda:
+            from .. import coarse
+            return coarse.forward(self, featvecs)[0]
         return self.point_decoder([featvecs.unsqueeze(1)])
 
 
@@ -38,6 +51,7 @@ class LIST(nn.Module):
         self.vox_encoder_kind = getattr(config, "vox_encoder", "torch")
         if self.vox_encoder_kind not in ("torch", "hip"):
             raise ValueError(f"vox_encoder = {self.vox_encoder_kind!r}: 'torch' or 'hip'")
+        self.coarse_stage = _coarse_stage_of(config)
         self.vox_encoder = M.VoxelEncoder2(config.im_enc_layers)
         self.sdf_decoder = M.VoxelDecoder2(enc_feat_size, 256)
         self.sdf_decoder.precision = getattr(config, "precision", "bf16x3")
@@ -66,12 +80,18 @@ class LIST(nn.Module):
         feat_g, _ = self.im_encoder(img)
         img_cl, use_cl = self._apply_memory_format(img)
         feat_g2, feat_l2 = self.im_encoder2(img_cl)
-        pc = self.point_decoder([feat_g.unsqueeze(1)])
-        coarse = torch.max(self.point_mlp_coarse(pc), -1)[0].reshape(img.shape[0], -1)
-        if trans_mat is None:
-            code = torch.cat([coarse, feat_g2.reshape(img.shape[0], -1)], dim=1)
-            trans_mat = self.spatial_transformer(code).reshape(-1, 4, 3)
-        occ = self.create_occ(pc)
+        if self.coarse_stage == "hip" and feat_g.is_cuda:
+            from .. import coarse as coarse_hip
+            pc, _, tm, occ = coarse_hip.forward(self, feat_g, feat_g2 if trans_mat is None else None, self.vox_res,
+                                                self.bb_min, self.bb_max)
+            trans_mat = tm if trans_mat is None else trans_mat
+        else:
+            pc = self.point_decoder([feat_g.unsqueeze(1)])
+            coarse = torch.max(self.point_mlp_coarse(pc), -1)[0].reshape(img.shape[0], -1)
+            if trans_mat is None:
+                code = torch.cat([coarse, feat_g2.reshape(img.shape[0], -1)], dim=1)
+                trans_mat = self.spatial_transformer(code).reshape(-1, 4, 3)
+            occ = self.create_occ(pc)
         if self.vox_encoder_kind == "hip" and occ.is_cuda:
             from .. import voxenc
             return feat_l2, voxenc.forward(self.vox_encoder, occ), trans_mat, pc, occ   # fp16 channels-last levels

@@ -59,6 +59,11 @@ with torch.no_grad():
     t, vh = timed(lambda: voxenc.encode(occ, pk))
     err = max(float((a.float() - b).abs().max()) for a, b in zip(vh, vox))
     print(f"vox_encoder HIP (fp16 MFMA)   {t:8.3f} ms   max|diff| vs fp32 {err:.3e}")
+    from list_amd import coarse                                                # --coarse_stage hip
+    cp = coarse.pack(net)
+    t, ch = timed(lambda: coarse.decode(cp, feat_g, feat_g2, cfg.vox_res, cfg.bb_min, cfg.bb_max))
+    print(f"coarse stage HIP (decoder, point MLP, camera, occupancy) {t:8.3f} ms   max|pc diff| vs torch "
+          f"{float((ch[0] - pc).abs().max()):.3e}")
     net2 = utils.get_class("network.models.LIST")(cfg).to(dev).eval()          # plain NCDHW encoder
     net2.vox_encoder.load_state_dict(net.vox_encoder.state_dict())
     t, _ = timed(lambda: net2.vox_encoder(occ))
