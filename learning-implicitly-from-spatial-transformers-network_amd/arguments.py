@@ -96,6 +96,10 @@ def build_parser():
     p.add_argument("--coarse_stage", default="torch", choices=["torch", "hip"],
                    help="hip: the stage between the image encoders and the 3-D encoder (tree decoder, point MLP, camera, "
                         "occupancy) runs in HIP (coarse.py); eval mode and no gradients only.  Training keeps 'torch'")
+    p.add_argument("--img_encoder", default="torch", choices=["torch", "hip"],
+                   help="hip: the two ResEncoders' inference forward runs in HIP (imgenc.py: fp32 stem, every other "
+                        "convolution on the matrix cores with fp16 operands, fp32 channels-last levels used in place by the "
+                        "query path); eval mode and no gradients only.  Training keeps 'torch'")
     p.add_argument("--channels_last", type=_bool, default=True,
                    help="run the encoders that feed the query path in channels-last memory format")
     p.add_argument("--synthetic_len", type=int, default=64, help="items per epoch of the synthetic datasets")

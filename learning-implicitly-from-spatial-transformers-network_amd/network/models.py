@@ -16,6 +16,22 @@ def _coarse_stage_of(config):
     return kind
 
 
+def _img_encoder_of(config):
+    """"hip": the ResEncoders' inference forward runs in HIP (imgenc.py) for tensors on a HIP device; eval mode and no
+    gradients only (a call in train() raises, it never falls back)."""
+    kind = getattr(config, "img_encoder", "torch")
+    if kind not in ("torch", "hip"):
+        raise ValueError(f"img_encoder = {kind!r}: 'torch' or 'hip'")
+    return kind
+
+
+def _encode_image(kind, encoder, img):
+    if kind == "hip" and img.is_cuda:
+        from .. import imgenc
+        return imgenc.forward(encoder, img)
+    return encoder(img)
+
+
 class CoarseNet(nn.Module):
     """RGB image -> coarse point cloud [B, prod(point_degree), 3]."""
 
@@ -25,9 +41,10 @@ class CoarseNet(nn.Module):
         self.point_decoder = M.TreeGraphDecoder(config.train_batch_size, config.point_feat,
                                                 config.point_degree, 10)
         self.coarse_stage = _coarse_stage_of(config)
+        self.img_encoder_kind = _img_encoder_of(config)
 
     def forward(self, rgba):
-        featvecs, _ = self.image_encoder(rgba)
+        featvecs, _ = _encode_image(self.img_encoder_kind, self.image_encoder, rgba)
         if self.coarse_stage == "hip" and featvecs.is_cuda:
             from .. import coarse
             return coarse.forward(self, featvecs)[0]
@@ -52,6 +69,7 @@ class LIST(nn.Module):
         if self.vox_encoder_kind not in ("torch", "hip"):
             raise ValueError(f"vox_encoder = {self.vox_encoder_kind!r}: 'torch' or 'hip'")
         self.coarse_stage = _coarse_stage_of(config)
+        self.img_encoder_kind = _img_encoder_of(config)
         self.vox_encoder = M.VoxelEncoder2(config.im_enc_layers)
         self.sdf_decoder = M.VoxelDecoder2(enc_feat_size, 256)
         self.sdf_decoder.precision = getattr(config, "precision", "bf16x3")
@@ -77,9 +95,9 @@ class LIST(nn.Module):
         return img, False
 
     def encode(self, img, trans_mat=None):
-        feat_g, _ = self.im_encoder(img)
+        feat_g, _ = _encode_image(self.img_encoder_kind, self.im_encoder, img)
         img_cl, use_cl = self._apply_memory_format(img)
-        feat_g2, feat_l2 = self.im_encoder2(img_cl)
+        feat_g2, feat_l2 = _encode_image(self.img_encoder_kind, self.im_encoder2, img_cl)
         if self.coarse_stage == "hip" and feat_g.is_cuda:
             from .. import coarse as coarse_hip
             pc, _, tm, occ = coarse_hip.forward(self, feat_g, feat_g2 if trans_mat is None else None, self.vox_res,

@@ -4,7 +4,8 @@ VoxelDecoder2 :192-282, VoxelEncoder2 :401-442, ResEncoder :1027-1074).
 
 Same class names, constructor arguments, forward signatures, attribute and state-dict names.  The two
 hot-path modules (PerceptualPooling, VoxelDecoder2) run on the HIP library; the per-image encoders
-stay PyTorch (MIOpen convolutions), as SURVEY section 8 scopes them.
+are PyTorch modules (MIOpen convolutions) whose inference forwards also exist in HIP, opt-in
+(voxenc.py, imgenc.py).
 """
 import torch
 import torch.nn as nn

@@ -73,3 +73,8 @@ with torch.no_grad():
     print(f"vox_encoder NCDHW fp32 + benchmark(find) {t:8.3f} ms")
     t, _ = timed(lambda: net.vox_encoder(occ), n=5)
     print(f"vox_encoder NDHWC fp32 + benchmark(find) {t:8.3f} ms")
+    from list_amd import imgenc                                                # --img_encoder hip
+    ip = imgenc.pack(net.im_encoder2)
+    t, (vh, fh) = timed(lambda: imgenc.encode(ip, img_cl))
+    err = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip([vh] + fh, [feat_g2] + feat_l2))
+    print(f"im_encoder2 HIP (fp16 MFMA)   {t:8.3f} ms   max relative diff vs fp32 {err:.3e}")
