@@ -18,7 +18,8 @@ SOURCES = ["prep_kernels.hip", "gather_kernels.hip", "gather_box_kernels.hip", "
            "bwd_scatter_kernels.hip", "bwd_box_kernels.hip", "list_capi.hip",
            "mesh_kernels.hip", "eval_kernels.hip", "data_kernels.hip", "loss_kernels.hip",
            "refine_kernels.hip", "voxenc_kernels.hip", "coarse_kernels.hip", "imgenc_kernels.hip"]
-HEADERS = ["list_common.h", "list_host.h", "point_math.h", "gather_math.h", "mfma_common.h", "box_partition.h", "mc_tables.h"]
+HEADERS = ["list_common.h", "list_host.h", "point_math.h", "gather_math.h", "mfma_common.h", "box_partition.h", "mc_tables.h",
+           "stage_prep.h"]
 PUBLIC_HEADERS = ["list_hip.h", "list_mesh.h", "list_eval.h", "list_data.h", "list_loss.h", "list_refine.h", "list_voxenc.h",
                   "list_coarse.h", "list_imgenc.h"]
 OBJ_DIR = os.path.join(CSRC, "_obj")

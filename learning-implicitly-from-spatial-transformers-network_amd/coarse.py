@@ -20,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import hip
+from . import hip, stage
 
 MAX_LAYERS, MAX_R, CODE, GROUP, TILE = 8, 256, 512, 16, 64
 MLP_WIDTHS = (3, 64, 256, 512)
@@ -88,8 +88,7 @@ def _lists(shape):
 
 
 # ---- closed forms of the two buffer sizes (the C side is the authority; the tests compare) ---------------------------
-def _align(n):
-    return (n + 255) // 256 * 256
+_align = stage.align256
 
 
 def _nodes(degrees, l):
@@ -161,7 +160,8 @@ def params_of(model, branch=True):
     out = {"features": features, "degrees": [l["degree"] for l in layers], "layers": layers, "mlp": None, "cam": None}
 
     def bn(m):
-        return {"g": _np(m.weight), "b": _np(m.bias), "m": _np(m.running_mean), "v": _np(m.running_var), "eps": float(m.eps)}
+        s = stage.state_numpy(m)
+        return {"g": s["weight"], "b": s["bias"], "m": s["running_mean"], "v": s["running_var"], "eps": float(m.eps)}
     if mlp is not None:
         out["mlp"] = [{"w": _np(blk[0].weight).reshape(blk[0].weight.shape[0], -1), "b": _np(blk[0].bias), "bn": bn(blk[1])}
                       for blk in (mlp.block1, mlp.block2, mlp.block3)]
@@ -186,10 +186,7 @@ def compose(loop0, loop1, dtype=np.float32):
 
 def bn_affine(bn, exact=False):
     """Eval-mode BN as y * s + t.  fp32: s = g / sqrt(v + eps), t = b - m * s, each operation rounded; exact: float64."""
-    ty = np.float64 if exact else np.float32
-    g, b, m, v = (np.asarray(bn[k]).astype(ty) for k in ("g", "b", "m", "v"))
-    s = (g / np.sqrt(v + ty(bn["eps"]), dtype=ty)).astype(ty)
-    return s, (b - (m * s).astype(ty)).astype(ty)
+    return stage.bn_affine(bn["g"], bn["b"], bn["m"], bn["v"], bn["eps"], exact)
 
 
 class Packed:
@@ -207,17 +204,11 @@ def _prep(model):
     import torch
     dec, mlp, cam = _parts(model)
     dev = next(dec.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError(f"coarse.pack: the module is on {dev}; the HIP coarse stage needs it on a HIP device")
+    stage.require_hip_module("coarse.pack", dev)
     params = params_of(model, branch=False)                       # W_branch stays on the device: never copied
     shape = shape_of_params(params)
     need = weight_bytes(shape)
-    keep = []
-
-    def ptr(a):
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        keep.append(t)
-        return t.data_ptr()
+    ptr, keep = stage.f32_pointers(dev)
     p = _Params()
     for l, lay in enumerate(params["layers"]):
         for i, w in enumerate(lay["root"]):
@@ -239,8 +230,8 @@ def _prep(model):
             raise RuntimeError("coarse.pack: W_branch must be a contiguous, 16-byte aligned float32 parameter (it is "
                                f"read in place): {w.dtype}, contiguous = {w.is_contiguous()}")
         branches.append(w)
+    blob = stage.new_blob(dev, need)
     with torch.cuda.device(dev):
-        blob = torch.zeros((need,), dtype=torch.uint8, device=dev)
         _check(load().list_coarse_prep_weights(C.byref(shape), C.byref(p), blob.data_ptr(), need, hip._stream()),
                "list_coarse_prep_weights")
     return Packed(blob, shape, branches)          # (`keep` is released stream-ordered by the caching allocator)
@@ -257,15 +248,7 @@ def _module_tensors(model):
 def pack(model):
     """Prepared weights of the stage, cached on the module and keyed as voxenc.pack is: the SAME parameter and buffer
     tensors with unchanged version counters, storage addresses and devices."""
-    tensors = _module_tensors(model)
-    key = tuple((id(t), t._version, t.data_ptr(), str(t.device), t.dtype) for t in tensors)
-    cached = model.__dict__.get("_coarse_pack")
-    if cached is not None and cached[0] == key and all(a is b for a, b in zip(cached[1], tensors)):
-        return cached[2]
-    model.__dict__["_coarse_pack"] = None
-    packed = _prep(model)
-    model.__dict__["_coarse_pack"] = (key, tensors, packed)
-    return packed
+    return stage.pack_cached(model, "_coarse_pack", _module_tensors(model), lambda: _prep(model))
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
@@ -380,37 +363,16 @@ def time_steps(packed, feat_g, feat_g2=None, vox_res=None, reps=10):
     def run(b, e):
         _check(lib.list_coarse_forward_steps(C.byref(packed.shape), C.byref(io), b, e, hip._stream()),
                "list_coarse_forward_steps")
-    out = []
     with torch.cuda.device(packed.device):
-        run(0, n)
-        for s in range(n):
-            ts = []
-            for _ in range(reps):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                run(s, s + 1)
-                b.record()
-                b.synchronize()
-                ts.append(a.elapsed_time(b))
-            out.append(float(np.median(ts)))
-    return out
+        return stage.time_launches(run, n, reps)
 
 
 def forward(model, feat_g, feat_g2=None, vox_res=None, bb_min=-0.5, bb_max=0.5):
     """The stage in HIP for an eval-mode model on a HIP device: decode(pack(model), ...).  Raises -- and never falls
     back to the torch modules -- when the model is in training mode (batch-statistics BN is not implemented) or when
     autograd would record the call (the stage has no HIP backward)."""
-    import torch
     mods = [m for m in _parts(model) if m is not None]
-    if any(m.training for m in mods):
-        raise RuntimeError("coarse_stage='hip' is the inference forward only: the model is in training mode "
-                           "(batch-statistics BatchNorm and the backward are not implemented in HIP).  Call .eval(), "
-                           "or train with --coarse_stage torch")
-    if torch.is_grad_enabled() and (feat_g.requires_grad or (feat_g2 is not None and feat_g2.requires_grad)
-                                    or any(p.requires_grad for m in mods for p in m.parameters())):
-        raise RuntimeError("coarse_stage='hip' has no backward: gradients are required here (grad mode is on and the "
-                           "stage's inputs or parameters require them).  Wrap the call in torch.no_grad(), or use "
-                           "--coarse_stage torch")
+    stage.refuse_training_and_grad("coarse_stage", "stage", mods, [feat_g, feat_g2])
     return decode(pack(model), feat_g, feat_g2, vox_res, bb_min, bb_max)
 
 

@@ -456,8 +456,7 @@ int list_coarse_prep_weights(const ListCoarseShape* shape, const ListCoarseParam
     return fail(LIST_ERR_ARG, "list_coarse_prep_weights: %s is NULL", params ? "packed" : "params");
   const ListCoarseShape& S = *shape;
   const PackedLayout P = packed_layout(S);
-  if (packed_bytes < P.total)
-    return fail(LIST_ERR_WORKSPACE, "list_coarse_prep_weights: packed holds %zu bytes, need %zu", packed_bytes, P.total);
+  if (packed_bytes < P.total) return packed_too_small("list_coarse_prep_weights", packed_bytes, P.total);
   const int L = S.n_degrees;
   for (int l = 0; l < L; ++l) {
     for (int i = 0; i <= l; ++i)
@@ -519,7 +518,7 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
   const int L = S.n_degrees;
   for (int l = 0; l < L; ++l) {
     if (!A.w_branch[l]) return fail(LIST_ERR_ARG, "list_coarse_forward: w_branch[%d] is NULL", l);
-    if ((uintptr_t)A.w_branch[l] % 16 != 0)
+    if (misaligned(A.w_branch[l], 16))
       return fail(LIST_ERR_ARG, "list_coarse_forward: w_branch[%d] is not 16-byte aligned", l);
   }
   if (A.coarse && !S.has_mlp) return fail(LIST_ERR_ARG, "list_coarse_forward: coarse asked for, the shape has no point MLP");
@@ -537,12 +536,9 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
   }
   const PackedLayout P = packed_layout(S);
   const WorkspaceLayout W = workspace_layout(S, A.B);
-  if (A.packed_bytes < P.total)
-    return fail(LIST_ERR_WORKSPACE, "list_coarse_forward: packed holds %zu bytes, need %zu", A.packed_bytes, P.total);
+  if (A.packed_bytes < P.total) return packed_too_small("list_coarse_forward", A.packed_bytes, P.total);
   if (A.workspace_bytes < W.total) return workspace_too_small(A.workspace_bytes, W.total, "list_coarse_workspace_bytes");
-  const int n_steps = n_steps_of(S);
-  if (step_begin < 0 || step_end > n_steps || step_begin > step_end)
-    return fail(LIST_ERR_ARG, "list_coarse_forward_steps: steps [%d, %d) outside [0, %d]", step_begin, step_end, n_steps);
+  if (int rc = check_step_range("list_coarse_forward_steps", step_begin, step_end, n_steps_of(S))) return rc;
 
   hipStream_t s = (hipStream_t)stream;
   const char* pk = (const char*)A.packed;
@@ -597,7 +593,7 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
       if (!A.occ) continue;
       const int64_t n = (int64_t)B * A.R * A.R * A.R;
       // a tensor's storage is 16-byte aligned where an allocator made it; a view that is not is cleared by floats
-      const int64_t n4 = (uintptr_t)A.occ % 16 == 0 ? n / 4 : 0;
+      const int64_t n4 = misaligned(A.occ, 16) ? 0 : n / 4;
       const int64_t work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
       hipLaunchKernelGGL(coarse_clear_kernel, dim3(blocks_for(work)), dim3(kThreads), 0, s, (float4*)A.occ, n4, A.occ, n);
       e = hipGetLastError();

@@ -21,6 +21,7 @@
 #include "list_host.h"
 #include "list_imgenc.h"
 #include "mfma_common.h"
+#include "stage_prep.h"
 
 namespace {
 
@@ -413,18 +414,6 @@ __global__ __launch_bounds__(kThreads) void imgenc_stem_pack_kernel(const float*
   if (idx < kStemK * kStemC) out[idx] = w[(idx % kStemC) * kStemK + idx / kStemC];
 }
 
-__global__ __launch_bounds__(kThreads) void imgenc_bn_kernel(const float* __restrict__ weight,
-                                                              const float* __restrict__ bias,
-                                                              const float* __restrict__ mean,
-                                                              const float* __restrict__ var, float eps, int n,
-                                                              float* __restrict__ s, float* __restrict__ t) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const float sc = weight[i] / sqrtf(var[i] + eps);
-  s[i] = sc;
-  t[i] = bias[i] - mean[i] * sc;
-}
-
 // fc1 o fc in float64, rounded once: wt[k][n] = sum_j fc1_w[n][j] fc_w[j][k]; bias[n] = sum_j fc1_w[n][j] fc_b[j] + fc1_b[n]
 __global__ __launch_bounds__(kThreads) void imgenc_compose_kernel(const float* __restrict__ fc_w,
                                                                    const float* __restrict__ fc_b,
@@ -446,8 +435,6 @@ __global__ __launch_bounds__(kThreads) void imgenc_compose_kernel(const float* _
 
 unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 int check_io(const ListImgencIO* io, const Net& net, const char* what) {
   if (!io) return fail(LIST_ERR_ARG, "%s: io is NULL", what);
   if (int rc = check_shape(io->B, io->H, io->W)) return rc;
@@ -465,8 +452,7 @@ int check_io(const ListImgencIO* io, const Net& net, const char* what) {
     if (misaligned(io->levels_out[k], 16))
       return fail(LIST_ERR_ARG, "%s: levels_out[%d] is not 16-byte aligned", what, k);
   const size_t need_p = packed_layout(net).total;
-  if (io->packed_bytes < need_p)
-    return fail(LIST_ERR_WORKSPACE, "%s: packed holds %zu bytes, need %zu", what, io->packed_bytes, need_p);
+  if (io->packed_bytes < need_p) return packed_too_small(what, io->packed_bytes, need_p);
   const size_t need_w = workspace_layout(net, io->B, io->H, io->W).total;
   if (io->workspace_bytes < need_w)
     return workspace_too_small(io->workspace_bytes, need_w, "list_imgenc_workspace_bytes");
@@ -494,8 +480,7 @@ int list_imgenc_prep_weights(const ListImgencParams* params, void* packed, size_
   if (misaligned(packed, 16)) return fail(LIST_ERR_ARG, "list_imgenc_prep_weights: packed is not 16-byte aligned");
   const Net net = make_net();
   const PackedLayout P = packed_layout(net);
-  if (packed_bytes < P.total)
-    return fail(LIST_ERR_WORKSPACE, "list_imgenc_prep_weights: packed holds %zu bytes, need %zu", packed_bytes, P.total);
+  if (packed_bytes < P.total) return packed_too_small("list_imgenc_prep_weights", packed_bytes, P.total);
   for (int c = 0; c < kConvs; ++c) {
     const ListImgencConv& cv = params->conv[c];
     if (!cv.w) return fail(LIST_ERR_ARG, "list_imgenc_prep_weights: conv[%d].w is NULL", c);
@@ -519,8 +504,8 @@ int list_imgenc_prep_weights(const ListImgencParams* params, void* packed, size_
       hipLaunchKernelGGL(imgenc_pack_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, cv.w, st.cin, st.cout, st.ks,
                          (_Float16*)(base + slot.w), total);
     }
-    hipLaunchKernelGGL(imgenc_bn_kernel, dim3(blocks_for(st.cout)), dim3(kThreads), 0, s, cv.bn_weight, cv.bn_bias,
-                       cv.bn_mean, cv.bn_var, cv.bn_eps, st.cout, (float*)(base + slot.s), (float*)(base + slot.t));
+    list::launch_bn_fold(cv.bn_weight, cv.bn_bias, cv.bn_mean, cv.bn_var, cv.bn_eps, st.cout, (float*)(base + slot.s),
+                         (float*)(base + slot.t), s);
     if (int rc = launched("list_imgenc_prep_weights")) return rc;
   }
   hipLaunchKernelGGL(imgenc_compose_kernel, dim3(blocks_for((kC4 + 1) * kVec)), dim3(kThreads), 0, s, params->fc_w,
@@ -531,8 +516,7 @@ int list_imgenc_prep_weights(const ListImgencParams* params, void* packed, size_
 int list_imgenc_forward_steps(const ListImgencIO* io, int32_t step_begin, int32_t step_end, void* stream) {
   const Net net = make_net();
   if (int rc = check_io(io, net, "list_imgenc_forward")) return rc;
-  if (step_begin < 0 || step_end > kSteps || step_begin > step_end)
-    return fail(LIST_ERR_ARG, "list_imgenc_forward_steps: steps [%d, %d) outside [0, %d]", step_begin, step_end, kSteps);
+  if (int rc = check_step_range("list_imgenc_forward_steps", step_begin, step_end, kSteps)) return rc;
   const PackedLayout P = packed_layout(net);
   const int B = io->B, H = io->H, W = io->W;
   const WorkspaceLayout WS = workspace_layout(net, B, H, W);

@@ -38,6 +38,20 @@ static int workspace_too_small(size_t have, size_t need, const char* sizing_fn) 
   return fail(LIST_ERR_WORKSPACE, "workspace %zu bytes, need %zu (%s)", have, need, sizing_fn);
 }
 
+// Refusal of a packed-weights blob smaller than the section's list_*_weight_bytes asks for
+static int packed_too_small(const char* what, size_t have, size_t need) {
+  return fail(LIST_ERR_WORKSPACE, "%s: packed holds %zu bytes, need %zu", what, have, need);
+}
+
+// LIST_OK when [begin, end) is a range of the n launches of a list_*_forward_steps (`what`), else its refusal
+static int check_step_range(const char* what, int32_t begin, int32_t end, int32_t n) {
+  if (begin < 0 || end > n || begin > end)
+    return fail(LIST_ERR_ARG, "%s: steps [%d, %d) outside [0, %d]", what, begin, end, n);
+  return LIST_OK;
+}
+
+static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }      // a: a power of two
+
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace regions start on 256 bytes
 
 static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -18,6 +18,7 @@
 #include "list_host.h"
 #include "list_voxenc.h"
 #include "mfma_common.h"
+#include "stage_prep.h"
 
 namespace {
 
@@ -398,18 +399,6 @@ __global__ __launch_bounds__(kThreads) void voxenc_copy_kernel(const float* __re
   if (i < n) out[i] = in[i];
 }
 
-__global__ __launch_bounds__(kThreads) void voxenc_bn_kernel(const float* __restrict__ weight,
-                                                              const float* __restrict__ bias,
-                                                              const float* __restrict__ mean,
-                                                              const float* __restrict__ var, float eps, int n,
-                                                              float* __restrict__ s, float* __restrict__ t) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const float sc = weight[i] / sqrtf(var[i] + eps);
-  s[i] = sc;
-  t[i] = bias[i] - mean[i] * sc;
-}
-
 unsigned blocks_for(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
@@ -438,8 +427,7 @@ int list_voxenc_prep_weights(const ListVoxencStage* stages, const int32_t* layer
   if (int rc = check_layers(layers, n_layers)) return rc;
   if (!stages || !packed) return fail(LIST_ERR_ARG, "list_voxenc_prep_weights: %s is NULL", stages ? "packed" : "stages");
   const PackedLayout P = packed_layout(layers);
-  if (packed_bytes < P.total)
-    return fail(LIST_ERR_WORKSPACE, "list_voxenc_prep_weights: packed holds %zu bytes, need %zu", packed_bytes, P.total);
+  if (packed_bytes < P.total) return packed_too_small("list_voxenc_prep_weights", packed_bytes, P.total);
   for (int l = 0; l < kStages; ++l) {
     const ListVoxencStage& st = stages[l];
     if (!st.conv_w || !st.conv_b) return fail(LIST_ERR_ARG, "list_voxenc_prep_weights: stage %d: conv_w or conv_b is NULL", l);
@@ -473,9 +461,8 @@ int list_voxenc_prep_weights(const ListVoxencStage* stages, const int32_t* layer
       bn_slot = &P.conv2[l];
     }
     if (bn_slot)
-      hipLaunchKernelGGL(voxenc_bn_kernel, dim3(blocks_for(cout)), dim3(kThreads), 0, s, st.bn_weight, st.bn_bias,
-                         st.bn_mean, st.bn_var, st.bn_eps, cout, (float*)(base + bn_slot->s),
-                         (float*)(base + bn_slot->t));
+      list::launch_bn_fold(st.bn_weight, st.bn_bias, st.bn_mean, st.bn_var, st.bn_eps, cout, (float*)(base + bn_slot->s),
+                           (float*)(base + bn_slot->t), s);
     if (int rc = launched("list_voxenc_prep_weights")) return rc;
   }
   return LIST_OK;
@@ -493,14 +480,9 @@ int list_voxenc_forward_steps(const float* occ, int32_t B, int32_t R, const int3
     if (!levels_out[k]) return fail(LIST_ERR_ARG, "list_voxenc_forward: levels_out[%d] is NULL", k);
   const PackedLayout P = packed_layout(layers);
   const WorkspaceLayout W = workspace_layout(B, R, layers);
-  if (packed_bytes < P.total)
-    return fail(LIST_ERR_WORKSPACE, "list_voxenc_forward: packed holds %zu bytes, need %zu", packed_bytes, P.total);
-  if (workspace_bytes < W.total)
-    return fail(LIST_ERR_WORKSPACE, "list_voxenc_forward: workspace holds %zu bytes, need %zu", workspace_bytes,
-                W.total);
-  const int n_steps = 3 + 2 * (kStages - 3);
-  if (step_begin < 0 || step_end > n_steps || step_begin > step_end)
-    return fail(LIST_ERR_ARG, "list_voxenc_forward_steps: steps [%d, %d) outside [0, %d]", step_begin, step_end, n_steps);
+  if (packed_bytes < P.total) return packed_too_small("list_voxenc_forward", packed_bytes, P.total);
+  if (workspace_bytes < W.total) return workspace_too_small(workspace_bytes, W.total, "list_voxenc_workspace_bytes");
+  if (int rc = check_step_range("list_voxenc_forward_steps", step_begin, step_end, 3 + 2 * (kStages - 3))) return rc;
 
   hipStream_t s = (hipStream_t)stream;
   const char* pk = (const char*)packed;

@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import hip
+from . import hip, stage
 
 N_LEVELS, N_CONVS, MIN_HW, MAX_HW, VEC, FC = 5, 20, 32, 512, 128, 1000
 LEVEL_CHANNELS = (64, 64, 128, 256, 512)
@@ -100,8 +100,7 @@ def n_steps():
 
 
 # ---- closed forms of the two buffer sizes (the C side is the authority; the tests compare) ---------------------------
-def _align(n):
-    return (n + 255) // 256 * 256
+_align = stage.align256
 
 
 def weight_bytes_closed_form():
@@ -135,10 +134,6 @@ def workspace_bytes(B, H, W):
 
 
 # ---- parameters ------------------------------------------------------------------------------------------------------
-def _module_tensors(module):
-    return list(module.parameters()) + list(module.buffers())
-
-
 def _bn_of(module, prefix):
     m = module
     for part in prefix.split("."):
@@ -149,7 +144,7 @@ def _bn_of(module, prefix):
 def params_of(module):
     """The encoder's parameters as numpy arrays: {"state": state_dict as numpy, "eps": BN prefix -> eps} -- what
     encode_cpu reads."""
-    return {"state": {k: v.detach().cpu().numpy() for k, v in module.state_dict().items()},
+    return {"state": stage.state_numpy(module),
             "eps": {s.bn: float(_bn_of(module, s.bn).eps) for s in CONV_STEPS}}
 
 
@@ -175,15 +170,9 @@ class Packed:
 def _prep(module):
     import torch
     dev = next(module.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError(f"imgenc.pack: the module is on {dev}; the HIP encoder needs it on a HIP device")
+    stage.require_hip_module("imgenc.pack", dev)
     need = weight_bytes()
-    keep = []
-
-    def ptr(t):
-        t = t.detach().to(torch.float32).contiguous()
-        keep.append(t)
-        return t.data_ptr()
+    ptr, keep = stage.f32_pointers()
     p = _Params()
     for i, s in enumerate(CONV_STEPS):
         bn = _bn_of(module, s.bn)
@@ -192,26 +181,18 @@ def _prep(module):
         c.bn_weight, c.bn_bias, c.bn_mean, c.bn_var = ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var)
         c.bn_eps = float(bn.eps)
     p.fc_w, p.fc_b, p.fc1_w, p.fc1_b = ptr(module.fc.weight), ptr(module.fc.bias), ptr(module.fc1.weight), ptr(module.fc1.bias)
+    blob = stage.new_blob(dev, need)
     with torch.cuda.device(dev):
-        blob = torch.zeros((need,), dtype=torch.uint8, device=dev)
         _check(load().list_imgenc_prep_weights(C.byref(p), blob.data_ptr(), need, hip._stream()),
                "list_imgenc_prep_weights")
     return Packed(blob)
 
 
 def pack(module):
-    """Prepared weights of a ResEncoder, cached on the module.  The cache holds for the SAME parameter and buffer tensors
-    with unchanged version counters, storage addresses and devices: an optimizer step, load_state_dict (an in-place
-    copy: the versions move), module.to() or .half() all rebuild."""
-    tensors = _module_tensors(module)
-    key = tuple((id(t), t._version, t.data_ptr(), str(t.device), t.dtype) for t in tensors)
-    cached = module.__dict__.get("_imgenc_pack")
-    if cached is not None and cached[0] == key and all(a is b for a, b in zip(cached[1], tensors)):
-        return cached[2]
-    module.__dict__["_imgenc_pack"] = None
-    packed = _prep(module)
-    module.__dict__["_imgenc_pack"] = (key, tensors, packed)
-    return packed
+    """Prepared weights of a ResEncoder, cached on the module for its parameter and buffer tensors as they are
+    (stage.pack_cached: an optimizer step, load_state_dict, module.to() or .half() all rebuild)."""
+    tensors = list(module.parameters()) + list(module.buffers())
+    return stage.pack_cached(module, "_imgenc_pack", tensors, lambda: _prep(module))
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
@@ -299,21 +280,11 @@ def time_steps(packed, img, reps=10):
     buffers = _buffers(packed, img)
     io = _io(packed, img, buffers)
     lib = load()
-    n = lib.list_imgenc_n_steps()
-    out = []
+
+    def run(b, e):
+        _check(lib.list_imgenc_forward_steps(C.byref(io), b, e, hip._stream()), "list_imgenc_forward_steps")
     with torch.cuda.device(img.device):
-        _check(lib.list_imgenc_forward_steps(C.byref(io), 0, n, hip._stream()), "list_imgenc_forward_steps")
-        for s in range(n):
-            ts = []
-            for _ in range(reps):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                _check(lib.list_imgenc_forward_steps(C.byref(io), s, s + 1, hip._stream()), "list_imgenc_forward_steps")
-                b.record()
-                b.synchronize()
-                ts.append(a.elapsed_time(b))
-            out.append(float(np.median(ts)))
-    return out
+        return stage.time_launches(run, lib.list_imgenc_n_steps(), reps)
 
 
 def step_flops(B, H, W):
@@ -347,15 +318,7 @@ def forward(module, img):
     """ResEncoder.forward in HIP for an eval-mode module on a HIP device.  Raises -- and never falls back to the torch
     module -- when the module is in training mode (batch-statistics BN is not implemented), when autograd would record
     the call (there is no HIP backward of the encoder), or when the module is not on a HIP device."""
-    import torch
-    if module.training:
-        raise RuntimeError("img_encoder='hip' is the inference forward only: the module is in training mode "
-                           "(batch-statistics BatchNorm and the backward are not implemented in HIP).  Call .eval(), "
-                           "or train with --img_encoder torch")
-    if torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in module.parameters())):
-        raise RuntimeError("img_encoder='hip' has no backward: gradients are required here (grad mode is on and the "
-                           "encoder's parameters require them).  Wrap the call in torch.no_grad(), or use "
-                           "--img_encoder torch")
+    stage.refuse_training_and_grad("img_encoder", "encoder", [module], [img])
     return encode(pack(module), img)
 
 
@@ -389,15 +352,8 @@ def _pool(x):
 
 def bn_affine(state, eps, prefix, exact=False):
     """s, t of the BN `prefix`: in fp32, operation for operation as the device's prep computes them, or in float64."""
-    g, b = np.asarray(state[prefix + ".weight"]), np.asarray(state[prefix + ".bias"])
-    m, v = np.asarray(state[prefix + ".running_mean"]), np.asarray(state[prefix + ".running_var"])
-    if exact:
-        s = g.astype(np.float64) / np.sqrt(v.astype(np.float64) + eps)
-        return s, b.astype(np.float64) - m.astype(np.float64) * s
-    f32 = np.float32
-    g, b, m, v = g.astype(f32), b.astype(f32), m.astype(f32), v.astype(f32)
-    s = (g / np.sqrt(v + f32(eps), dtype=f32)).astype(f32)
-    return s, (b - (m * s).astype(f32)).astype(f32)
+    return stage.bn_affine(state[prefix + ".weight"], state[prefix + ".bias"], state[prefix + ".running_mean"],
+                           state[prefix + ".running_var"], eps, exact)
 
 
 def compose_head(state, dtype=np.float32):

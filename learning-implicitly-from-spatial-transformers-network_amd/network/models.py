@@ -7,21 +7,14 @@ import torch.nn as nn
 from . import modules as M
 
 
-def _coarse_stage_of(config):
-    """"hip": the stage between the image encoders and the 3-D encoder runs in HIP (coarse.py) for tensors on a HIP
-    device; eval mode and no gradients only (a call in train() raises, it never falls back)."""
-    kind = getattr(config, "coarse_stage", "torch")
+def _kind_of(config, name):
+    """The option `name`: "vox_encoder" (the 3-D encoder, voxenc.py), "coarse_stage" (the stage between the image
+    encoders and the 3-D encoder, coarse.py) or "img_encoder" (the ResEncoders, imgenc.py).  "hip": that part's
+    inference forward runs in HIP for tensors on a HIP device; eval mode and no gradients only -- the training forward
+    and the backward are the torch module's (a call in train() raises, it never falls back)."""
+    kind = getattr(config, name, "torch")
     if kind not in ("torch", "hip"):
-        raise ValueError(f"coarse_stage = {kind!r}: 'torch' or 'hip'")
-    return kind
-
-
-def _img_encoder_of(config):
-    """"hip": the ResEncoders' inference forward runs in HIP (imgenc.py) for tensors on a HIP device; eval mode and no
-    gradients only (a call in train() raises, it never falls back)."""
-    kind = getattr(config, "img_encoder", "torch")
-    if kind not in ("torch", "hip"):
-        raise ValueError(f"img_encoder = {kind!r}: 'torch' or 'hip'")
+        raise ValueError(f"{name} = {kind!r}: 'torch' or 'hip'")
     return kind
 
 
@@ -40,8 +33,8 @@ class CoarseNet(nn.Module):
         self.image_encoder = M.ResEncoder()
         self.point_decoder = M.TreeGraphDecoder(config.train_batch_size, config.point_feat,
                                                 config.point_degree, 10)
-        self.coarse_stage = _coarse_stage_of(config)
-        self.img_encoder_kind = _img_encoder_of(config)
+        self.coarse_stage = _kind_of(config, "coarse_stage")
+        self.img_encoder_kind = _kind_of(config, "img_encoder")
 
     def forward(self, rgba):
         featvecs, _ = _encode_image(self.img_encoder_kind, self.image_encoder, rgba)
@@ -63,13 +56,9 @@ class LIST(nn.Module):
         # list_prep_vox_maps is a no-op (MIOpen NDHWC/NHWC convolutions: same results, same speed).
         self.channels_last = bool(getattr(config, "channels_last", True))
         self.vox_encoder_half = getattr(config, "vox_encoder_precision", "fp32") == "fp16"
-        # "hip": the eval-mode forward of the 3-D encoder runs in HIP (voxenc.py) for tensors on a HIP device; the
-        # training forward and the backward are the torch module's (a forward in train() raises, it never falls back)
-        self.vox_encoder_kind = getattr(config, "vox_encoder", "torch")
-        if self.vox_encoder_kind not in ("torch", "hip"):
-            raise ValueError(f"vox_encoder = {self.vox_encoder_kind!r}: 'torch' or 'hip'")
-        self.coarse_stage = _coarse_stage_of(config)
-        self.img_encoder_kind = _img_encoder_of(config)
+        self.vox_encoder_kind = _kind_of(config, "vox_encoder")
+        self.coarse_stage = _kind_of(config, "coarse_stage")
+        self.img_encoder_kind = _kind_of(config, "img_encoder")
         self.vox_encoder = M.VoxelEncoder2(config.im_enc_layers)
         self.sdf_decoder = M.VoxelDecoder2(enc_feat_size, 256)
         self.sdf_decoder.precision = getattr(config, "precision", "bf16x3")

@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import hip
+from . import hip, stage
 
 N_LAYERS, N_LEVELS, MAX_R = 9, 6, 256
 N_STAGES = N_LAYERS - 1
@@ -52,8 +52,7 @@ def _layers_arg(layers):
 
 
 # ---- closed forms of the two buffer sizes (the C side is the authority; the tests compare) ---------------------------
-def _align(n):
-    return (n + 255) // 256 * 256
+_align = stage.align256
 
 
 def _wpk_bytes(cin, cout):
@@ -97,15 +96,11 @@ def workspace_bytes(B, R, layers):
 
 
 # ---- parameters ------------------------------------------------------------------------------------------------------
-def _module_tensors(module):
-    return list(module.parameters()) + list(module.buffers())
-
-
 def params_of(module):
     """The encoder's parameters as numpy arrays: {"layers", "eps": per stage, "state": state_dict as numpy} -- what
     encode_cpu reads."""
     return {"layers": [int(c) for c in module.layers], "eps": [float(b.eps) for b in module.bn],
-            "state": {k: v.detach().cpu().numpy() for k, v in module.state_dict().items()}}
+            "state": stage.state_numpy(module)}
 
 
 class Packed:
@@ -123,15 +118,9 @@ def _prep(module):
     import torch
     layers = [int(c) for c in module.layers]
     dev = next(module.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError(f"voxenc.pack: the module is on {dev}; the HIP encoder needs it on a HIP device")
+    stage.require_hip_module("voxenc.pack", dev)
     need = weight_bytes(layers)
-    keep = []
-
-    def ptr(t):
-        t = t.detach().to(torch.float32).contiguous()
-        keep.append(t)
-        return t.data_ptr()
+    ptr, keep = stage.f32_pointers()
     stages = (_Stage * N_STAGES)()
     for l in range(N_STAGES):
         conv, bn = module.conv[f"conv_{l}"], module.bn[l]
@@ -144,26 +133,18 @@ def _prep(module):
         st.bn_mean, st.bn_var = ptr(bn.running_mean), ptr(bn.running_var)
         st.bn_eps = float(bn.eps)
     arr, n = _layers_arg(layers)
+    blob = stage.new_blob(dev, need)
     with torch.cuda.device(dev):
-        blob = torch.zeros((need,), dtype=torch.uint8, device=dev)
         _check(load().list_voxenc_prep_weights(stages, arr, n, blob.data_ptr(), need, hip._stream()),
                "list_voxenc_prep_weights")
     return Packed(blob, layers)
 
 
 def pack(module):
-    """Prepared weights of a VoxelEncoder2, cached on the module.  The cache holds for the SAME parameter and buffer
-    tensors with unchanged version counters, storage addresses and devices: an optimizer step, load_state_dict (an
-    in-place copy: the versions move), module.to() or .half() all rebuild."""
-    tensors = _module_tensors(module)
-    key = tuple((id(t), t._version, t.data_ptr(), str(t.device), t.dtype) for t in tensors)
-    cached = module.__dict__.get("_voxenc_pack")
-    if cached is not None and cached[0] == key and all(a is b for a, b in zip(cached[1], tensors)):
-        return cached[2]
-    module.__dict__["_voxenc_pack"] = None
-    packed = _prep(module)
-    module.__dict__["_voxenc_pack"] = (key, tensors, packed)
-    return packed
+    """Prepared weights of a VoxelEncoder2, cached on the module for its parameter and buffer tensors as they are
+    (stage.pack_cached: an optimizer step, load_state_dict, module.to() or .half() all rebuild)."""
+    tensors = list(module.parameters()) + list(module.buffers())
+    return stage.pack_cached(module, "_voxenc_pack", tensors, lambda: _prep(module))
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
@@ -274,35 +255,15 @@ def time_steps(occ, packed, reps=10):
         _check(lib.list_voxenc_forward_steps(occ.data_ptr(), B, R, arr, n, packed.blob.data_ptr(),
                                              packed.blob.numel(), ws.data_ptr(), ws.numel(), outs, b, e,
                                              hip._stream()), "list_voxenc_forward_steps")
-    out = []
     with torch.cuda.device(occ.device):
-        run(0, n_steps)
-        for s in range(n_steps):
-            ts = []
-            for _ in range(reps):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                run(s, s + 1)
-                b.record()
-                b.synchronize()
-                ts.append(a.elapsed_time(b))
-            out.append(float(np.median(ts)))
-    return out
+        return stage.time_launches(run, n_steps, reps)
 
 
 def forward(module, occ):
     """VoxelEncoder2.forward in HIP for an eval-mode module on a HIP device.  Raises -- and never falls back to the
     torch module -- when the module is in training mode (batch-statistics BN is not implemented) or when autograd
     would record the call (there is no HIP backward of the encoder yet)."""
-    import torch
-    if module.training:
-        raise RuntimeError("vox_encoder='hip' is the inference forward only: the module is in training mode "
-                           "(batch-statistics BatchNorm and the backward are not implemented in HIP).  Call .eval(), "
-                           "or train with --vox_encoder torch")
-    if torch.is_grad_enabled() and (occ.requires_grad or any(p.requires_grad for p in module.parameters())):
-        raise RuntimeError("vox_encoder='hip' has no backward: gradients are required here (grad mode is on and the "
-                           "encoder's parameters require them).  Wrap the call in torch.no_grad(), or use "
-                           "--vox_encoder torch")
+    stage.refuse_training_and_grad("vox_encoder", "encoder", [module], [occ])
     return encode(occ, pack(module))
 
 
@@ -352,14 +313,8 @@ def encode_cpu(occ, params, storage="fp16", start=None, stop_after=None):
         return (w.astype(np.float16) if half else w).astype(np.float64)
 
     def affine(l):
-        g, b = np.asarray(st[f"bn.{l}.weight"]), np.asarray(st[f"bn.{l}.bias"])
-        m, v = np.asarray(st[f"bn.{l}.running_mean"]), np.asarray(st[f"bn.{l}.running_var"])
-        if exact:
-            s = g.astype(np.float64) / np.sqrt(v.astype(np.float64) + eps[l])
-            return s, b.astype(np.float64) - m.astype(np.float64) * s
-        g, b, m, v = g.astype(f32), b.astype(f32), m.astype(f32), v.astype(f32)
-        s = (g / np.sqrt(v + f32(eps[l]), dtype=f32)).astype(f32)
-        return s, (b - (m * s).astype(f32)).astype(f32)
+        return stage.bn_affine(st[f"bn.{l}.weight"], st[f"bn.{l}.bias"], st[f"bn.{l}.running_mean"],
+                               st[f"bn.{l}.running_var"], eps[l], exact)
 
     def conv(x, name, half):
         z = _conv3(x.astype(np.float64), weight(f"conv.{name}.weight", half))

@@ -17,6 +17,7 @@ import _voxenc_check as vc  # noqa: E402
 
 U24 = vc.U24                        # unit roundoff of fp32
 ratios = vc.ratios                  # error / bound per element; NaN and the infinities compared by class
+half_bound = vc.half_bound          # the bound of an fp16 output: plus the storage rounding
 
 
 class Launch:
@@ -104,11 +105,6 @@ def reference(L, x, idt=None, pad=None):
         if step.relu:
             y = np.where(y < 0, 0.0, y)                          # (a NaN stays a NaN)
     return y, bound
-
-
-def half_bound(y, bound):
-    ya = np.where(np.isfinite(y), np.abs(y), 0.0)
-    return bound + 2.0 ** -11 * (ya + bound) + 2.0 ** -25
 
 
 def check(L, x, idt=None, act=None, level=None):

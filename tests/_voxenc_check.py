@@ -7,7 +7,7 @@ launch's OWN input as the device held it (a bit-exact copy), so nothing compound
 output element has its own bound (`reference`)."""
 import numpy as np
 
-from list_amd import voxenc
+from list_amd import stage, voxenc
 
 U24 = 2.0 ** -24                    # unit roundoff of fp32
 F16_OVERFLOW = 65520.0              # round-to-nearest-even gives an infinity from here on (65504 + half an ulp)
@@ -38,13 +38,9 @@ class Launch:
 
 
 def bn_affine(state, eps, l):
-    """s, t of stage l in fp32, operation for operation as voxenc_bn_kernel computes them (fp32 add, correctly rounded
-    sqrt and division, fp32 multiply and subtract)."""
-    f32 = np.float32
-    g, b = np.asarray(state[f"bn.{l}.weight"]).astype(f32), np.asarray(state[f"bn.{l}.bias"]).astype(f32)
-    m, v = np.asarray(state[f"bn.{l}.running_mean"]).astype(f32), np.asarray(state[f"bn.{l}.running_var"]).astype(f32)
-    s = (g / np.sqrt(v + f32(eps), dtype=f32)).astype(f32)
-    return s, (b - (m * s).astype(f32)).astype(f32)
+    """s, t of stage l in fp32, operation for operation as the device's prep computes them (stage.bn_affine)."""
+    return stage.bn_affine(state[f"bn.{l}.weight"], state[f"bn.{l}.bias"], state[f"bn.{l}.running_mean"],
+                           state[f"bn.{l}.running_var"], eps)
 
 
 def launches(params):
@@ -70,6 +66,13 @@ def launches(params):
         s, t = bn_affine(st, eps[l], l)
         out.append(Launch(f"conv_{l}_0", l, True, w, b, s.astype(f64), t.astype(f64), "relu_bn", True, True, w32))
     return out
+
+
+def half_bound(y, head):
+    """`head` plus the storage term of an fp16 output: half an ulp of the value that is rounded, 2^-11 (|y| + head), or
+    half a subnormal step, 2^-25."""
+    ya = np.where(np.isfinite(y), np.abs(y), 0.0)
+    return head + 2.0 ** -11 * (ya + head) + 2.0 ** -25
 
 
 def reference(x, L):
@@ -123,10 +126,7 @@ def reference(x, L):
                 head = np.abs(L.s) * e_acc + 3 * U24 * (np.abs(L.s) * (rr + e_acc) + np.abs(L.t))
             else:
                 y, head = r, e_acc
-        bound = head
-        if L.half:
-            ya = np.where(np.isfinite(y), np.abs(y), 0.0)
-            bound = head + 2.0 ** -11 * (ya + head) + 2.0 ** -25
+        bound = half_bound(y, head) if L.half else head
     return y, bound, head
 
 

@@ -16,34 +16,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-import numpy as np  # noqa: E402
 import torch        # noqa: E402
+
+from _timing import interleaved  # noqa: E402
 
 DEV = "cuda:0"
 RES = 224
-
-
-def time_events(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms))
-
-
-def interleaved(fns, iters, warmup, rounds):
-    best = {k: float("inf") for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            best[k] = min(best[k], time_events(fn, iters, warmup))
-    return best
 
 
 def main():
