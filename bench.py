@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- SDF query-points/sec of the LIST hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3             # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full      # ... and everything else the benchmark measures and checks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +12,12 @@ already resident in HBM in the REFERENCE's layout (NCHW / NCDHW fp32 feature map
 plus, for N > 1 ranks, the RCCL all-gather of the SDF shards (the loss-reduction exchange).
 Each rank owns B images (weak scaling: the batch x query axis is sharded, no other collective).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the line: `value`, `ms_per_step`, and what the timed steps' own HIP events give (`step_events_ms`,
+`kernel_ms` at the coarse boundaries, the `roofline` of fc_0, `path_rates`).  Every measurement or check that takes steps
+of its own runs with --full only: the per-gather detail steps, the sustained leg, the other precisions and layouts, the
+training step, --whole-model, the CPU baseline with its parity legs, and with N > 1 ranks the exchange check and the rank
+census.  The timed region is the same in both.
 """
 import argparse
 import ctypes
@@ -151,13 +157,13 @@ def kernel_table(B, N, img_res, vox_res, map_size, x_bytes_per_feature, map_byte
 
 
 # LIST_BENCH_FORCE_EXCHANGE=1: a ONE-rank process group takes the N > 1 code path (process group, exchange buffers,
-# asynchronous all-gather, exchange check, rank census): the RCCL pre-flight on a one-GPU box
+# asynchronous all-gather; with --full also the exchange check and the rank census): the RCCL pre-flight on a one-GPU box
 # (tests/test_rccl_preflight_gpu.py, with LIST_FORCE_COLLECTIVES=1 for list_amd.parallel).  Never a scaling number.
 FORCE_EXCHANGE = os.environ.get("LIST_BENCH_FORCE_EXCHANGE", "0") == "1"
 
 
 def run_config(args, precision, steps, warmup, inp, hip, ev, world, device, gather_fn, sustained_steps=0, fused_fc0=True,
-               img_proj=None, keep_last=False):
+               img_proj=None, keep_last=False, full=True):
     import torch
     import torch.distributed as dist
     multi = world > 1 or FORCE_EXCHANGE
@@ -184,7 +190,8 @@ def run_config(args, precision, steps, warmup, inp, hip, ev, world, device, gath
             *[None if (coarse and i % n_ev in apart) else ev.create() for i in range(n_ev * n_chunks)])
         return pre, arr
     step_events = [event_sets(True) for _ in range(steps)]
-    detail_events = [event_sets(False) for _ in range(DETAIL_STEPS)]
+    # (full=False, a plain run: no untimed step behind the timed region, no check of what the exchange delivered)
+    detail_events = [event_sets(False) for _ in range(DETAIL_STEPS)] if full else []
     # N > 1: the exchange of step i (one RCCL all-gather of the SDF shards) runs on RCCL's stream beside the kernels
     # of step i+1; two output buffers alternate, and a step first orders itself after the gather that last read its buffer
     # (strong scaling: the global batch may not divide by the ranks -- every rank exchanges a buffer of B_pad =
@@ -320,12 +327,16 @@ def run_config(args, precision, steps, warmup, inp, hip, ev, world, device, gath
         # fc_0 produced the perceptual block of its A operand on chip (k_fc0_fused): no 2-D gather kernel ran
         kernel_ms["_fused_fc0"] = 1
     kernel_ms["gathers_back_to_back"] = group / steps       # the same seven launches as they run in the timed region
-    kernel_ms["gathers_one_by_one_sum"] = float(sum(acc[3 + s] for s in range(first, hip.STAGE_IMG + 1)))   # (untimed steps)
+    if detail_events:
+        kernel_ms["gathers_one_by_one_sum"] = float(sum(acc[3 + s] for s in range(first, hip.STAGE_IMG + 1)))   # (untimed steps)
+    else:
+        for s in range(first, hip.STAGE_IMG + 1):          # no step timed the gathers apart: no entry, rather than a zero
+            del kernel_ms[names[3 + s]]
     kernel_ms["_launches_per_step"] = n_chunks
     # HIP-event time of every timed step (first launch .. behind the last one, on the stream they run on)
     step_ms = sorted(ev.elapsed_ms(pre[0], pre[4]) for pre, _ in step_events)
     q = lambda f: step_ms[min(len(step_ms) - 1, int(f * len(step_ms)))]
-    if multi:
+    if multi and full:
         # once, outside the timed region: what the exchange delivered holds this rank's shard at this rank's offset, and
         # every other rank's rows are finite numbers (not the zeros the buffer was born with)
         rank = dist.get_rank()
@@ -682,13 +693,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="list_im2sdf_b8_n20k_224", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run everything else the benchmark measures and checks: per-gather detail "
+                         "steps, the sustained leg, the other precisions and layouts, the training step, the CPU baseline "
+                         "and its parity legs, with N > 1 ranks the exchange check and the rank census; the options that "
+                         "shape those legs (--no-*, --sustained-steps, --cpu-sample-*) mean nothing without it")
     ap.add_argument("--precision", default=None, choices=["fp16", "bf16x3", "bf16"],
-                    help="MLP arithmetic; default: headline fp16 plus a shorter bf16x3 run reported under 'alt'")
+                    help="MLP arithmetic of the headline (default fp16; bf16x3 on the grid workload); with --full, leaving it "
+                         "out also runs the other precisions, reported under 'alt' and 'alt_bf16'")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-channels-last-alt", action="store_true")
     ap.add_argument("--no-train-step", action="store_true")
     ap.add_argument("--whole-model", action="store_true",
-                    help="also time the whole LIST.forward (encoders included) on the same B x N")
+                    help="with --full: also time the whole LIST.forward (encoders included) on the same B x N")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank owns the workload's B images (BASELINE config 2 per GPU); strong: BASELINE "
                          "config 3 -- a global batch of --global-batch images split over the ranks")
@@ -709,6 +726,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if args.whole_model and not args.full:
+        ap.error("--whole-model is a measurement of its own: it needs --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started the way the driver starts the N = 1 case (`python bench.py --gpus N`, no launcher): this process
@@ -788,13 +807,14 @@ def main():
     headline = args.precision or ("bf16x3" if grid else "fp16")
     alt_prec = "fp16" if headline == "bf16x3" else "bf16x3"
     elapsed, kernel_ms, sdf, extra = run_config(args, headline, args.steps, args.warmup, inp, hip, ev, world,
-                                                device, gather_fn, sustained_steps=args.sustained_steps,
-                                                keep_last=bool(args.dump_outputs))
+                                                device, gather_fn, sustained_steps=args.sustained_steps if args.full else 0,
+                                                keep_last=bool(args.dump_outputs), full=args.full)
     if args.dump_outputs and rank == 0:
         written = dump_outputs(args.dump_outputs, extra.pop("last_outputs"))
         print(f"bench: last timed step's outputs written to {args.dump_outputs}: {json.dumps(written)}", file=sys.stderr)
     alt_cl = None
-    if args.precision is None and not args.no_channels_last_alt:
+    more = args.full and args.precision is None          # the legs beside the headline: other precisions, layouts, training
+    if more and not args.no_channels_last_alt:
         # same workload with the maps already in the layout MI355X-first producers emit (SURVEY 8 f2:
         # channels_last / channels_last_3d encoders, as network.models.LIST runs them): the 3-D
         # hand-off becomes zero-copy, the 2-D resize reads NHWC
@@ -815,7 +835,7 @@ def main():
                           "the in-model query rate by this ratio")
         del inp_cl
     alt = None
-    if args.precision is None:
+    if more:
         a_steps = max(2, args.steps // 2)
         a_el, a_ms, a_sdf, a_extra = run_config(args, alt_prec, a_steps, min(args.warmup, 2), inp, hip, ev, world,
                                                 device, gather_fn)
@@ -824,7 +844,7 @@ def main():
                "max_abs_diff_vs_headline": float((a_sdf - sdf).abs().max())}
 
     alt_unfused = None
-    if args.precision is None and kernel_ms.get("_fused_fc0"):
+    if more and kernel_ms.get("_fused_fc0"):
         # the same step with fc_0 as the plain GEMM it was until round 3 (k_gather_img writes the perceptual block into X,
         # k_gemm_nt_pp reads it back): the MFMA roofline of fc_0 ALONE, beside the fused kernel's (whose time also holds
         # the bilinear sampling of 1024 channels per point)
@@ -838,7 +858,7 @@ def main():
                        "bit_identical_to_headline": bool(torch.equal(u_sdf, sdf))}
         assert alt_unfused["bit_identical_to_headline"]
     alt_bf16 = None
-    if args.precision is None and "bf16" not in (headline, alt_prec):
+    if more and "bf16" not in (headline, alt_prec):
         # BASELINE config 2 says "bf16": the plain-bf16 mode (one MFMA product per MAC on bf16 operands, fp32 maps) as
         # a third first-class mode of the line, with its stated tolerance (5e-3 absolute) and both parity legs below
         b_steps = max(2, args.steps // 2)
@@ -849,7 +869,7 @@ def main():
                     "max_abs_diff_vs_headline": float((b_sdf - sdf).abs().max())}
 
     alt_img_proj = None
-    if args.precision is None and not grid and alt is not None:
+    if more and not grid and alt is not None:
         # list_prep_img_proj (ABI 8) on / off beside what the modes above ran: the fp16 headline with it forced on (the
         # 2-D sample then leaves fc_0 again: k_gather_img + k_gemm_nt_pp with a row-vector epilogue), the bf16x3 mode
         # with it forced off (the round-3 path)
@@ -871,7 +891,7 @@ def main():
 
     train = None
     train_grads = None
-    if args.precision is None and not args.no_train_step and B * N <= 262144:
+    if more and not args.no_train_step and B * N <= 262144:
         train, train_grads = run_train_step(headline, max(2, args.steps // 2), min(args.warmup, 2), inp, hip, ev)
         # the same training step with fp32-grade gradients (bf16 hi+lo operands): the parity-grade number
         t3, _ = run_train_step("bf16x3", max(2, args.steps // 4), min(args.warmup, 2), inp, hip, ev)
@@ -898,7 +918,7 @@ def main():
         whole = run_whole_model(args.workload, headline, device)
 
     ranks = None
-    if multi:
+    if multi and args.full:
         # what the collective backend really spans: every rank's id and timed-region wall clock through an all-gather
         # round trip (nccl = RCCL on device tensors; the gloo rehearsal stages through the host)
         on = device if dist.get_backend() == "nccl" else "cpu"
@@ -974,7 +994,7 @@ def main():
     parity = None
     parity_leg = None
     modes = {}
-    if not args.no_cpu_baseline and not multi:
+    if args.full and not args.no_cpu_baseline and not multi:
         from oracle import torch_ops as TO
         ns = min(args.cpu_sample_images, B)
         cq = inp["query"][:ns].cpu()
@@ -1025,7 +1045,7 @@ def main():
             ref_big = TO.list_query(cq, ci, cv, ct, {k: v.cpu() for k, v in big_w.items()}, **kw)
             tolerance = TOLERANCE
             modes = {}
-            for prec in dict.fromkeys([headline, alt_prec, "bf16"] if args.precision is None else [headline]):
+            for prec in dict.fromkeys([headline, alt_prec, "bf16"] if more else [headline]):
                 legs = {"bench_distribution": leg(forward(prec, inp["weights"]), ref),
                         "sdf_about_0.5": leg(forward(prec, big_w), ref_big)}
                 tol = tolerance[prec]
@@ -1072,7 +1092,7 @@ def main():
                   else "SDF query-points/sec",
         "value": value, "unit": "query-points/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": args.scaling, "vs_baseline": None,
+        "scaling": args.scaling, "vs_baseline": None, "full": args.full,
         "dtype": {"fp16": "fp16", "bf16": "bf16", "bf16x3": "bf16x3 (bf16 hi+lo operands, fp32-grade)"}[headline],
         "data": "synthetic",
         "config": {"workload": args.workload if args.scaling == "weak" else f"list_im2sdf_b{args.global_batch}_n20k_224 (BASELINE config 3)",
@@ -1102,7 +1122,8 @@ def main():
         "kernel_ms_note": "HIP-event intervals over the timed steps, except gather_vox_l1 .. gather_tail: the seven "
                           "gathers of a step are independent launches and run without queue barriers between them in "
                           "the timed region (gathers_back_to_back is their group, timed there) and with the barriers "
-                          f"in {DETAIL_STEPS} further untimed steps, which is where their individual durations come from",
+                          + (f"in {DETAIL_STEPS} further untimed steps, which is where their individual durations come from"
+                             if args.full else "only in the untimed steps of a --full run: their individual durations are not in this line"),
         "per_kernel": per_kernel,
         "path_rates": path,
         "parity_max_abs_err_vs_cpu": parity,

@@ -591,7 +591,7 @@ def query_chunks(n_points, packed):
     return (n_points + rows - 1) // rows
 
 
-# diagnostics (bench.py --whole-model): a ctypes array of hipEvent_t handles (N_STAGES per row chunk) recorded by the
+# diagnostics (bench.py --full --whole-model): a ctypes array of hipEvent_t handles (N_STAGES per row chunk) recorded by the
 # next inference queries that pass no stage_events of their own -- the stage times INSIDE LIST.forward
 STAGE_EVENTS_HOOK = None
 

@@ -50,3 +50,12 @@ def test_self_launch_happens_before_anything_touches_the_gpu():
     assert main.index("self_launch(args.gpus") < main.index("torch.cuda.")
     launcher = src[src.index("def self_launch("):src.index("def main():")]
     assert "torch.cuda" not in launcher and "exec" not in launcher.replace("sys.executable", "")
+
+
+def test_a_measurement_of_its_own_is_refused_without_full():
+    # a plain run does what its headline needs and nothing else: asking it for the whole-model leg is an error in the
+    # arguments (exit code 2, before anything is built or any device is opened), never a leg that is silently left out
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--whole-model"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]
+    assert not r.stdout.strip()

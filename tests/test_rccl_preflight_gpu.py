@@ -31,11 +31,11 @@ def test_one_rank_rccl_group_drives_every_collective_branch():
 def test_bench_step_with_the_exchange_on_a_one_rank_rccl_group():
     """bench.py's N > 1 step (query kernels + asynchronous all-gather on RCCL's stream, two alternating buffers,
     exchange check) as the driver launches it, with one rank: WORLD_SIZE = 1 under torch.distributed.run and
-    LIST_BENCH_FORCE_EXCHANGE=1."""
+    LIST_BENCH_FORCE_EXCHANGE=1.  --full: the exchange check and the rank census are not part of a plain run."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(LIST_BENCH_FORCE_EXCHANGE="1", LIST_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                        "--precision", "fp16", "--no-cpu-baseline", "--sustained-steps", "0"], env=env,
+                        "--full", "--precision", "fp16", "--no-cpu-baseline", "--sustained-steps", "0"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

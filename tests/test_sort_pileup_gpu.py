@@ -1,5 +1,5 @@
 """GPU: the point sort under key pile-up.  An untrained spatial transformer projects most query points onto the clamp
-of network/modules.py:43 (bench.py --whole-model: 88 %), i.e. thousands of points share a handful of pixel bins.  The
+of network/modules.py:43 (bench.py --full --whole-model: 88 %), i.e. thousands of points share a handful of pixel bins.  The
 sort groups equal keys inside a wave into one atomic (gather_kernels.hip, wave_grouped_add); this checks that the orders
 it builds are still permutations that group equal keys, and that the sorted forward equals the unsorted one bit for bit,
 for all-on-one-pixel, edge-piled and spread projections -- and with a point count that leaves the last wave partly idle."""
