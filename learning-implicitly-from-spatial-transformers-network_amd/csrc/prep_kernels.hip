@@ -148,6 +148,7 @@ __global__ __launch_bounds__(256) void k_prep_img_tile(ListMap2D m, int ms, int 
 static bool try_prep_img_tile(const ListMap2D& m, int B, int ms, int Ct, int coff, int f16, void* out,
                               hipStream_t s, hipError_t* e) {
   const int align = f16 ? 8 : 4;
+  // (tests/test_handoff_gpu.py RESIZE_RUNS: R4 takes this kernel, R7_ms274_fallback fails its LDS test at every XS)
   if (m.sw != 1 || (m.C % kTileG) != 0 || (coff % align) != 0 || (Ct % align) != 0 || ms < 2) return false;
   const float sy = (float)(m.H - 1) / (float)(ms - 1), sx = (float)(m.W - 1) / (float)(ms - 1);
   // rows per tile: as many as keep the staged source rows within ~32 KB, at most 8
@@ -224,6 +225,7 @@ __global__ __launch_bounds__(256) void k_prep_img_nhwc(ListMap2D m, int B, int m
 static bool try_prep_img_nhwc(const ListMap2D& m, int B, int ms, int Ct, int coff, int f16, void* out,
                               hipStream_t s, hipError_t* e) {
   const int vo = f16 ? 8 : 4;
+  // (tests/test_handoff_gpu.py RESIZE_RUNS: R5 and R6cl take this kernel; fp16 output declines R6cl's 36 and 20 channels)
   if (m.sc != 1 || (m.C % vo) != 0 || (coff % vo) != 0 || (Ct % vo) != 0 || (m.sw % 4) != 0 ||
       (m.sh % 4) != 0 || (m.sb % 4) != 0 || (reinterpret_cast<uintptr_t>(m.data) & 15) != 0)
     return false;
@@ -385,6 +387,8 @@ __global__ __launch_bounds__(kRowsPx * 8) void k_prep_img_rows(PrepRowsArgs a, v
   }
 }
 
+// (tests/test_handoff_gpu.py RESIZE_RUNS: R1 / R2 / R3 hold for every level -- pair / vec / plain strided loads --, one
+// 32-channel level sends R4, R5 and R7_ms274_fallback to the per-level kernels, R6 has no eligible level)
 static bool rows_eligible(const ListMap2D& m, int ms, int Ct, int coff) {
   return ms >= 2 && m.C >= kRowsCg && (m.C % kRowsCg) == 0 && (coff % 8) == 0 && (Ct % 8) == 0;
 }
@@ -414,6 +418,7 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
         lv.RY = ry < 2 ? 2 : (ry > kRowsRyMax ? kRowsRyMax : ry);
         lv.nyt = (map_size + lv.RY - 1) / lv.RY;
       }
+      // (vec: R2; otherwise the kernel's `pair` test, sw == 1 && W >= 2: R1; neither: R3, R3b)
       lv.vec = (m.sc == 1 && (m.sw % 4) == 0 && (m.sh % 4) == 0 && (m.sb % 4) == 0 &&
                 (reinterpret_cast<uintptr_t>(m.data) & 15) == 0) ? 1 : 0;
       wgs += (int64_t)B * lv.nyt * lv.cgroups * a.nxt;
@@ -436,6 +441,7 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
       coff += m.C;
       continue;
     }
+    // (tests/test_handoff_gpu.py RESIZE_RUNS: R6, R6cl in fp16, the *_generic runs and R7_ms274_fallback end here)
     dim3 grid(B * map_size, (m.C + kResizeCg - 1) / kResizeCg);
     hipLaunchKernelGGL(k_prep_img, grid, dim3(256), 0, s, m, map_size, Ct, coff, f16, out);
     hipError_t e = hipGetLastError();
