@@ -1160,10 +1160,21 @@ hipError_t launch_gemm(const GemmParams& p, int terms, int epi, hipStream_t s) {
     int tiles = 0;
     for (int i = 0; i < p.n_groups; ++i) {
       const GemmGroup& g = p.grp[i];
-      if (g.K % 64 || g.K <= 0 || g.m_tiles <= 0 || g.a_rows <= 0 || g.a_rows > g.m_tiles * BM || !g.a || !g.w || !g.out) return hipErrorInvalidValue;
+      if (g.K % 64 || g.K <= 0 || g.m_tiles <= 0 || g.a_rows <= 0 || g.a_rows > g.m_tiles * BM || (!g.a && !p.a_src) || !g.w || !g.out) return hipErrorInvalidValue;
       tiles += g.m_tiles;
     }
     if (tiles * BM != p.M || p.plain_loop) return hipErrorInvalidValue;   // (the 16x16x32 ping-pong kernel only)
+    if (p.a_src) {             // the A operands are NCHW fp32 levels: projected straight from the source (prep_kernels.hip)
+      if (p.fmt != FMT_FP16 || !p.dx_f16 || p.n_store != p.N || p.ldo != p.N || p.a_src_B < 1) return hipErrorInvalidValue;
+      const void* ws[kGemmMaxGroups];
+      void* outs[kGemmMaxGroups];
+      for (int i = 0; i < p.n_groups; ++i) {
+        const ListMap2D& m = p.a_src[i];
+        if (m.sw != 1 || m.C != p.grp[i].K || (int64_t)p.a_src_B * m.H * m.W != p.grp[i].a_rows) return hipErrorInvalidValue;
+        ws[i] = p.grp[i].w; outs[i] = p.grp[i].out;
+      }
+      return launch_proj_levels_nchw(p.a_src, ws, outs, p.n_groups, p.a_src_B, p.N, p.ldw, s, p.launch_order);
+    }
   }
   if (p.M % BM || p.N % BN || p.K % 64 || p.M <= 0) return hipErrorInvalidValue;
   if (p.x3i && p.fmt == FMT_FP16) return hipErrorInvalidValue;

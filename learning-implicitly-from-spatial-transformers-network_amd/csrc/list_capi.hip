@@ -520,9 +520,13 @@ int list_prep_img_proj(const ListMap2D maps[LIST_N_IMG_LEVELS], int32_t B, int32
   ListMap2D proj[LIST_N_IMG_LEVELS];
   int coff = pl.kept_C, n_proj = 0;
   char* sc = (char*)scratch;
-  // rows [B*H*W][C] of every projected level in the operand format (fp16, or bf16 hi / lo interleaved through an fp32
-  // staging copy): one launch
-  {
+  // fp16 operands on x-contiguous (NCHW) levels: the grouped launch below reads the levels themselves (k_proj_level_nchw:
+  // no operand rows in scratch) and, sharing no buffer with the kept levels' resize, follows it without a barrier
+  bool from_source = fp16;
+  for (int i = n_kept_levels; i < LIST_N_IMG_LEVELS; ++i) from_source = from_source && maps[i].sw == 1;
+  // otherwise rows [B*H*W][C] of every projected level in the operand format (fp16, or bf16 hi / lo interleaved through an
+  // fp32 staging copy): one launch
+  if (!from_source) {
     void* outs[LIST_N_IMG_LEVELS];
     for (int i = n_kept_levels; i < LIST_N_IMG_LEVELS; ++i) outs[i - n_kept_levels] = fp16 ? sc + pl.a_op[i] : sc + pl.a_f32[i];
     e = launch_img_level_rows(maps + n_kept_levels, outs, pl.n_proj, B, fp16 ? 1 : 0, s);
@@ -561,6 +565,7 @@ int list_prep_img_proj(const ListMap2D maps[LIST_N_IMG_LEVELS], int32_t B, int32
   gp.M = (int)m_total;
   gp.a_hi = gp.grp[0].a; gp.a_lo = gp.a_hi; gp.w_hi = gp.grp[0].w; gp.w_lo = gp.w_hi; gp.dx = gp.grp[0].out;
   gp.K = gp.grp[0].K; gp.lda = gp.grp[0].lda; gp.a_rows = gp.grp[0].a_rows;
+  if (from_source) { gp.a_src = maps + n_kept_levels; gp.a_src_B = B; gp.launch_order = n_kept_levels > 0 ? any_order() : 0; }
   e = launch_gemm(gp, precision == LIST_PREC_BF16X3 ? 3 : 1, EPI_DX, s);
   if (e != hipSuccess) return hip_fail(e, "level projection launch");
   e = launch_proj_resize_sum(proj, n_proj, B, map_size, Ct, pl.kept_C, fp16 ? 1 : 0, out, s, p16);

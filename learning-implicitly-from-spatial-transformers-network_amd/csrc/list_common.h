@@ -415,6 +415,11 @@ struct GemmParams {
   const float* smp_trans_mat;                                // [B][4][3]
   int smp_ms, smp_Ct, smp_coff; float smp_clamp_hi;          // map size, channels per pixel, first sampled channel (the kept ones lead)
   GatherParams smp_pts;                                      // the points behind the rows (query, order, perm, scale, N, p_begin, n_valid)
+  // grouped EPI_DX launch, fp16 operands (host side only, no kernel reads these): a_src != null = the A operand of group i
+  // is the encoder level a_src[i], [a_src_B, K, H, W] fp32 with x contiguous, read and rounded to halfs by the kernel
+  // itself (k_proj_level_nchw, prep_kernels.hip) instead of rows in memory; grp[i].a and lda are unused
+  const ListMap2D* a_src; int a_src_B;
+  int launch_order;                                          // 0, or any_order(): the launch before it on the stream is in order and shares no buffer with this one
 };
 
 // EPI_MASK_SPLIT: out = acc where the saved activation is positive (ReLU backward), no bias;
@@ -440,6 +445,11 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
 // list_prep_img_proj (prep_kernels.hip): encoder level [B,C,H,W] fp32 (any strides) -> rows [B*H*W][C], fp16 or fp32
 // (n levels in ONE launch: outs[i] receives maps[i])
 hipError_t launch_img_level_rows(const ListMap2D* maps, void* const* outs, int n, int B, int f16, hipStream_t s);
+// list_prep_img_proj, fp16 operands: P_i[B*H*W][H1] (halfs) = half(maps[i] as rows) x w[i][H1][ldw]^T (halfs, the level's
+// columns of the packed fc_0 weight) straight from the [B,C,H,W] fp32 sources, n levels in ONE launch; C % 64 == 0,
+// H1 % 256 == 0 (reached through launch_gemm: GemmParams.a_src)
+hipError_t launch_proj_levels_nchw(const ListMap2D* maps, const void* const* w, void* const* outs, int n, int B, int H1,
+                                   int ldw, hipStream_t s, int order);
 // out[b][y][x][coff + n] = sum_l resize(P_l)[b][y][x][n]: P_l = channels-last [B][H_l][W_l][H1] (n_src of them), out =
 // map with Ct channels per pixel; f16: out is halfs; src_f16: the P_l are halfs (strides of `src` then count halfs);
 // H1 % 64 == 0

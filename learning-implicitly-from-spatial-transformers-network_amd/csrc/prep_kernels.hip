@@ -250,14 +250,23 @@ static bool try_prep_img_nhwc(const ListMap2D& m, int B, int ms, int Ct, int cof
 // slots on arithmetic and index math than the 16-B store it feeds can hide).  No LDS: the 8 lanes of a
 // pixel read 8-channel groups of the same two taps (L1/L2 hits), and write one full 128-B line (fp16:
 // 64 channels; fp32: 256 B) per pixel, 8 pixels per wave-instruction.  Same bits as k_prep_img.
+//
+// XL, the lane-along-x form (round 9), for x-contiguous sources that are not strongly up-sampled (sx >= kRowsXlMinSx): the
+// thread still owns (output column, 8 channels) and runs the same statements, but a wave is one channel octet of 64
+// neighbouring columns instead of 8 columns of all 8 octets.  A pair load then reads 64 sx contiguous floats of ONE
+// channel plane (whole 128-B lines) where the form above touches 8 planes and uses 8 sx floats of each: 30 - 50 B of every
+// line it asks for, which nothing amortises on a down-sampled level (every output row fetches fresh source rows).  The
+// finished row turns through LDS so that the stores are whole lines again (see there).
 constexpr int kRowsPx = 16;                 // output columns per workgroup (x 8 channel octets = 128 threads)
+constexpr int kRowsPxXl = 64;               // ... of the lane-along-x form (x 8 channel octets = 8 waves)
+constexpr float kRowsXlMinSx = 0.5f;        // source columns per output column from which a level takes the XL form
 constexpr int kRowsCg = 64;                 // channels per workgroup
 constexpr int kRowsRyMax = 32;              // output rows per workgroup, at most
 struct PrepRowsLevel { ListMap2D m; int coff, wg_begin, cgroups, vec, RY, nyt; };
 struct PrepRowsArgs { PrepRowsLevel lv[LIST_N_IMG_LEVELS]; int n_levels, B, ms, Ct, nxt; };
 
-template <int F16>
-__global__ __launch_bounds__(kRowsPx * 8) void k_prep_img_rows(PrepRowsArgs a, void* __restrict__ out) {
+template <int F16, int XL>
+__global__ __launch_bounds__((XL ? kRowsPxXl : kRowsPx) * 8, XL ? 8 : 1) void k_prep_img_rows(PrepRowsArgs a, void* __restrict__ out) {
   // level-major block order: consecutive workgroups are x tiles of one (level, channel group, row block), 32 KB
   // apart in the output.  (Pixel-tile-major -- the 16 channel groups of a pixel tile side by side, so that a
   // pixel's 2 KB leave together -- measured 0.73 ms instead of 0.19: the writes of a moment then fall on few
@@ -280,8 +289,9 @@ __global__ __launch_bounds__(kRowsPx * 8) void k_prep_img_rows(PrepRowsArgs a, v
   const ListMap2D m = a.lv[l].m;
   const int coff = a.lv[l].coff, vec = a.lv[l].vec;
   const int ms = a.ms;
-  const int q = threadIdx.x & 7, xi = threadIdx.x >> 3;
-  const int xo = xt * kRowsPx + xi;
+  const int q = XL ? (int)(threadIdx.x >> 6) : (int)(threadIdx.x & 7);
+  const int xi = XL ? (int)(threadIdx.x & 63) : (int)(threadIdx.x >> 3);
+  const int xo = xt * (XL ? kRowsPxXl : kRowsPx) + xi;
   const bool active = xo < ms;
   const int x = active ? xo : ms - 1;
   const int c = cg * kRowsCg + 8 * q;
@@ -362,6 +372,54 @@ __global__ __launch_bounds__(kRowsPx * 8) void k_prep_img_rows(PrepRowsArgs a, v
     float o[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) o[k] = top[k] * wy0 + bot[k] * wy1;
+    if constexpr (XL) {
+      // the row's 64 pixels x 64 channels turn through LDS (16-B pieces, piece index ^ pixel & 7: no bank conflict either
+      // way; two buffers, so one barrier per row) and leave as whole lines, 8 lanes per pixel, like the form above.
+      // (Stored straight from the registers -- 16 B of 64 different lines per wave instruction, the 8 waves completing
+      // each line in L2 -- the store side alone took 39 - 45 us for 96 MB against 24 us for whole lines, and ate the
+      // gain of the loads at the metric's two kept levels: 67.8 -> 64.6 us.)
+      constexpr int NCH = F16 ? 1 : 2;                       // 16-B pieces per thread
+      __shared__ uint4 turn[2][kRowsPxXl * 8 * NCH];
+      uint4 piece[NCH];
+      if (F16) {
+        bool over = false;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) over = over || (fabsf(o[k]) > 65504.f);
+        if (over) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) o[k] = sat_h(o[k]);
+        }
+        const uint2 lo = half4_inrange(make_float4(o[0], o[1], o[2], o[3]));
+        const uint2 hi = half4_inrange(make_float4(o[4], o[5], o[6], o[7]));
+        piece[0] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+      } else {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j)
+          piece[j] = make_uint4(__builtin_bit_cast(unsigned, o[4 * j]), __builtin_bit_cast(unsigned, o[4 * j + 1]),
+                                __builtin_bit_cast(unsigned, o[4 * j + 2]), __builtin_bit_cast(unsigned, o[4 * j + 3]));
+      }
+      uint4* buf = turn[(y - y_first) & 1];
+#pragma unroll
+      for (int j = 0; j < NCH; ++j) buf[xi * (8 * NCH) + ((q * NCH + j) ^ (xi & 7))] = piece[j];
+      __syncthreads();
+      const int p = (int)(threadIdx.x >> 3), qq = (int)(threadIdx.x & 7);
+      const int xp = xt * kRowsPxXl + p;
+      if (xp < ms) {
+        const int64_t ob = ((int64_t)(b * ms + y) * ms + xp) * a.Ct + coff + cg * kRowsCg;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+          const int ch = j * 8 + qq;
+          const uint4 w = buf[p * (8 * NCH) + (ch ^ (p & 7))];
+          if (F16)
+            __builtin_nontemporal_store((f32x4){__builtin_bit_cast(float, w.x), __builtin_bit_cast(float, w.y),
+                                                __builtin_bit_cast(float, w.z), __builtin_bit_cast(float, w.w)},
+                                        (f32x4*)((unsigned short*)out + ob + ch * 8));
+          else
+            *(uint4*)((float*)out + ob + ch * 4) = w;
+        }
+      }
+      continue;
+    }
     if (!active) continue;
     if (F16) {
       // saturate only the rows that need it: one compare per value (|x| is a free source modifier; a NaN compares
@@ -393,22 +451,37 @@ static bool rows_eligible(const ListMap2D& m, int ms, int Ct, int coff) {
   return ms >= 2 && m.C >= kRowsCg && (m.C % kRowsCg) == 0 && (coff % 8) == 0 && (Ct % 8) == 0;
 }
 
+// (tests/test_handoff_coalesced_gpu.py: the lane-along-x form is taken level by level -- `pair` loads and sx >= kRowsXlMinSx;
+// a level just below the threshold, a channels-last one and the transposed views keep the form above)
+static bool rows_lane_along_x(const ListMap2D& m, int ms, int vec) {
+  return !vec && m.sw == 1 && m.W >= 2 && (float)(m.W - 1) / (float)(ms - 1) >= kRowsXlMinSx;
+}
+
 hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int map_size, int Ct,
                            int f16, void* out, hipStream_t s, int n_levels) {
   int coff = 0;
   if (n_levels <= 0) return hipSuccess;
   {
-    PrepRowsArgs a;
-    a.n_levels = 0; a.B = B; a.ms = map_size; a.Ct = Ct;
-    a.nxt = (map_size + kRowsPx - 1) / kRowsPx;
-    int64_t wgs = 0;
+    // a[0]: the levels of the 8-columns-by-8-octets form, a[1]: those of the lane-along-x form -- a launch each (they write
+    // different channels of the map: the second one goes without a barrier)
+    PrepRowsArgs a[2];
+    int64_t wgs[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+      a[k].n_levels = 0; a[k].B = B; a[k].ms = map_size; a[k].Ct = Ct;
+      const int px = k ? kRowsPxXl : kRowsPx;
+      a[k].nxt = (map_size + px - 1) / px;
+    }
     bool all = true;
     int co = 0;
     for (int i = 0; i < n_levels; ++i) {
       const ListMap2D& m = maps[i];
       if (!rows_eligible(m, map_size, Ct, co)) { all = false; break; }
-      PrepRowsLevel& lv = a.lv[a.n_levels++];
-      lv.m = m; lv.coff = co; lv.wg_begin = (int)wgs; lv.cgroups = m.C / kRowsCg;
+      // (vec: R2; otherwise the kernel's `pair` test, sw == 1 && W >= 2: R1; neither: R3, R3b)
+      const int vec = (m.sc == 1 && (m.sw % 4) == 0 && (m.sh % 4) == 0 && (m.sb % 4) == 0 &&
+                       (reinterpret_cast<uintptr_t>(m.data) & 15) == 0) ? 1 : 0;
+      const int k = rows_lane_along_x(m, map_size, vec) ? 1 : 0;
+      PrepRowsLevel& lv = a[k].lv[a[k].n_levels++];
+      lv.m = m; lv.coff = co; lv.wg_begin = (int)wgs[k]; lv.cgroups = m.C / kRowsCg; lv.vec = vec;
       // Output rows per workgroup.  A thread's rows form a chain of dependent source-row fetches (~2 us each):
       // about five fetches per workgroup everywhere -- few rows where every output row needs new source rows
       // (down-sampling: 2 per row), many where ten output rows share one (the 14 px level)
@@ -418,18 +491,24 @@ hipError_t launch_prep_img(const ListMap2D maps[LIST_N_IMG_LEVELS], int B, int m
         lv.RY = ry < 2 ? 2 : (ry > kRowsRyMax ? kRowsRyMax : ry);
         lv.nyt = (map_size + lv.RY - 1) / lv.RY;
       }
-      // (vec: R2; otherwise the kernel's `pair` test, sw == 1 && W >= 2: R1; neither: R3, R3b)
-      lv.vec = (m.sc == 1 && (m.sw % 4) == 0 && (m.sh % 4) == 0 && (m.sb % 4) == 0 &&
-                (reinterpret_cast<uintptr_t>(m.data) & 15) == 0) ? 1 : 0;
-      wgs += (int64_t)B * lv.nyt * lv.cgroups * a.nxt;
+      wgs[k] += (int64_t)B * lv.nyt * lv.cgroups * a[k].nxt;
+      if (wgs[k] >= 2147483647LL) { all = false; break; }
       co += m.C;
     }
-    if (all && wgs > 0 && wgs < 2147483647LL) {
-      if (f16)
-        hipLaunchKernelGGL(k_prep_img_rows<1>, dim3((unsigned)wgs), dim3(kRowsPx * 8), 0, s, a, out);
-      else
-        hipLaunchKernelGGL(k_prep_img_rows<0>, dim3((unsigned)wgs), dim3(kRowsPx * 8), 0, s, a, out);
-      return hipGetLastError();
+    if (all) {
+      int order = 0;
+      for (int k = 1; k >= 0; --k) {
+        if (wgs[k] <= 0) continue;
+        const dim3 grid((unsigned)wgs[k]), block((k ? kRowsPxXl : kRowsPx) * 8);
+        if (k && f16) LIST_LAUNCH((k_prep_img_rows<1, 1>), grid, block, 0, s, order, a[k], out);
+        else if (k) LIST_LAUNCH((k_prep_img_rows<0, 1>), grid, block, 0, s, order, a[k], out);
+        else if (f16) LIST_LAUNCH((k_prep_img_rows<1, 0>), grid, block, 0, s, order, a[k], out);
+        else LIST_LAUNCH((k_prep_img_rows<0, 0>), grid, block, 0, s, order, a[k], out);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        order = any_order();
+      }
+      return hipSuccess;
     }
   }
   for (int i = 0; i < n_levels; ++i) {
@@ -516,6 +595,127 @@ hipError_t launch_img_level_rows(const ListMap2D* maps, void* const* outs, int n
   a.blk_begin[LIST_N_IMG_LEVELS] = (int)blocks;
   if (f16) hipLaunchKernelGGL(k_img_level_rows<1>, dim3((unsigned)blocks), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_img_level_rows<0>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------------
+// list_prep_img_proj, fp16 operands on x-contiguous levels: P_l[pixel][n] = sum_c half(level[c][pixel]) W0[n][coff_l + c]
+// straight from the NCHW source, every projected level in ONE launch -- no operand rows in scratch, no queue boundary
+// between the rows and their product (reached through launch_gemm: a grouped EPI_DX launch with GemmParams.a_src).
+// A workgroup = 64 pixels of one image x 256 weight rows, 4 waves of 64 x 64 (4 x 4 accumulators of
+// v_mfma_f32_16x16x32_f16).  Per K-tile of 64 channels: the A tile is loaded as k_img_level_rows loads it (lanes along the
+// pixels, 8 channels per 16-B piece, half4's saturating rounding) into a swizzled LDS image [64][128 B], double-buffered;
+// a wave's W fragments (its own 64 weight rows: no other wave reads them) come from L2 in registers; both are requested
+// one K-tile ahead, over the MFMAs.  k ascends as in the grouped k_gemm_nt_pp launch this replaces (the projected levels
+// are the same bits, profiles/r09_2d_handoff.txt); the weight fragment is the FIRST MFMA operand, so a lane holds 4
+// consecutive n of one pixel: an 8-B store of halfs with EPI_DX's rounding (half4).
+// --------------------------------------------------------------------------------------------
+constexpr int kProjPx = 64, kProjN = 256;
+struct ProjLevelArgs {
+  ListMap2D m[LIST_N_IMG_LEVELS]; const unsigned short* w[LIST_N_IMG_LEVELS]; unsigned short* out[LIST_N_IMG_LEVELS];
+  int blk_begin[LIST_N_IMG_LEVELS + 1]; int n, B, H1, ldw;
+};
+
+__global__ __launch_bounds__(256) void k_proj_level_nchw(ProjLevelArgs a) {
+  __shared__ uint4 As[2][kProjPx * 8];
+  // blk_begin[r] belongs to level n - 1 - r: the last level (the longest K loop, 8 K-tiles at 512 channels) starts first
+  int r = 0;
+#pragma unroll
+  for (int i = 1; i < LIST_N_IMG_LEVELS; ++i)
+    if (i < a.n && (int)blockIdx.x >= a.blk_begin[i]) r = i;
+  const int l = a.n - 1 - r;
+  const ListMap2D m = a.m[l];
+  const int npx = m.H * m.W, pbs = (npx + kProjPx - 1) / kProjPx, nts = a.H1 / kProjN;
+  int idx = (int)blockIdx.x - a.blk_begin[r];
+  const int nt = idx % nts; idx /= nts;
+  const int pb = idx % pbs;
+  const int b = idx / pbs;
+  const int p0 = pb * kProjPx, n0 = nt * kProjN;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, ko = lane >> 4;                           // fragment row / column, k-octet of a k-step
+  // A loader: pixel `lane` of the tile, channel octets 2 wave and 2 wave + 1 of the K-tile
+  const int px = min(p0 + lane, npx - 1);
+  const int y = px / m.W, x = px - y * m.W;
+  const float* src = m.data + (int64_t)b * m.sb + (int64_t)y * m.sh + (int64_t)x * m.sw + (int64_t)(16 * wave) * m.sc;
+  const unsigned short* wrow = a.w[l] + (int64_t)(n0 + wave * 64 + col) * a.ldw + 8 * ko;
+  const int nk = m.C / 64;
+  float v[16];
+  auto fetch = [&](int t) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = src[(int64_t)(t * 64 + k) * m.sc];
+  };
+  f32x4v acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+  f16x8 bw[2][4], bn[2][4];          // W fragments of this K-tile and of the next one
+  auto fetch_w = [&](int t, f16x8 (&d)[2][4]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[ks][j] = *(const f16x8*)(wrow + (int64_t)(j * 16) * a.ldw + t * 64 + ks * 32);
+  };
+  fetch(0);
+  fetch_w(0, bw);
+#pragma unroll 1
+  for (int t = 0; t < nk; ++t) {
+    uint4* buf = As[t & 1];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const uint2 lo = half4(make_float4(v[8 * o], v[8 * o + 1], v[8 * o + 2], v[8 * o + 3]));
+      const uint2 hi = half4(make_float4(v[8 * o + 4], v[8 * o + 5], v[8 * o + 6], v[8 * o + 7]));
+      buf[lane * 8 + ((2 * wave + o) ^ (lane & 7))] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+    }
+    if (t + 1 < nk) { fetch(t + 1); fetch_w(t + 1, bn); }
+    __syncthreads();          // one barrier per K-tile: the buffer written now was last read two tiles ago
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      f16x8 fa[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        fa[i] = __builtin_bit_cast(f16x8, buf[(i * 16 + col) * 8 + ((4 * ks + ko) ^ (col & 7))]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bw[ks][j], fa[i], acc[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bw[ks][j] = bn[ks][j];
+  }
+  // acc[i][j][e] = P[pixel p0 + 16 i + col][n0 + 64 wave + 16 j + 4 ko + e]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int p = p0 + i * 16 + col;
+    if (p >= npx) continue;
+    unsigned short* o = a.out[l] + ((int64_t)b * npx + p) * a.H1 + n0 + wave * 64 + 4 * ko;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      *(uint2*)(o + j * 16) = half4(make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]));
+  }
+}
+
+hipError_t launch_proj_levels_nchw(const ListMap2D* maps, const void* const* w, void* const* outs, int n, int B, int H1,
+                                   int ldw, hipStream_t s, int order) {
+  if (n < 1 || n > LIST_N_IMG_LEVELS || B < 1 || H1 < kProjN || H1 % kProjN || ldw < 64 || ldw % 8) return hipErrorInvalidValue;
+  ProjLevelArgs a;
+  a.n = n; a.B = B; a.H1 = H1; a.ldw = ldw;
+  int64_t blocks = 0;
+  for (int r = 0; r < n; ++r) {                 // blocks in reverse level order (see the kernel)
+    const int i = n - 1 - r;
+    const ListMap2D& m = maps[i];
+    if (m.C < 64 || m.C % 64 || m.H < 1 || m.W < 1 || (reinterpret_cast<uintptr_t>(w[i]) & 15) ||
+        (reinterpret_cast<uintptr_t>(outs[i]) & 7))
+      return hipErrorInvalidValue;
+    a.m[i] = m; a.w[i] = (const unsigned short*)w[i]; a.out[i] = (unsigned short*)outs[i]; a.blk_begin[r] = (int)blocks;
+    blocks += (int64_t)B * ((m.H * m.W + kProjPx - 1) / kProjPx) * (H1 / kProjN);
+    if (blocks >= 2147483647LL) return hipErrorInvalidValue;
+  }
+  for (int i = n; i < LIST_N_IMG_LEVELS; ++i) { a.m[i] = a.m[0]; a.w[i] = a.w[0]; a.out[i] = a.out[0]; a.blk_begin[i] = (int)blocks; }
+  a.blk_begin[LIST_N_IMG_LEVELS] = (int)blocks;
+  LIST_LAUNCH(k_proj_level_nchw, dim3((unsigned)blocks), dim3(256), 0, s, order, a);
   return hipGetLastError();
 }
 
