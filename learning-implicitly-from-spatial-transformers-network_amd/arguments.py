@@ -100,6 +100,13 @@ def build_parser():
                    help="hip: the two ResEncoders' inference forward runs in HIP (imgenc.py: fp32 stem, every other "
                         "convolution on the matrix cores with fp16 operands, fp32 channels-last levels used in place by the "
                         "query path); eval mode and no gradients only.  Training keeps 'torch'")
+    p.add_argument("--stage2_loss", default="torch", choices=["torch", "hip"],
+                   help="hip: stage 2's loss (occupancy BCE and SDFLoss) and its gradients run in HIP on CUDA tensors "
+                        "(s2loss.py: one pass over the occupancy volume forward, one backward, float64 sums in a fixed "
+                        "order); 'torch' keeps the executor's torch expressions")
+    p.add_argument("--occ_dtype", default="float32", choices=["float32", "uint8"],
+                   help="dtype of the occupancy target 'occ' the IM2SDF datasets hand out: uint8 ships a quarter of the "
+                        "bytes to the device per step; both losses read it as it is")
     p.add_argument("--channels_last", type=_bool, default=True,
                    help="run the encoders that feed the query path in channels-last memory format")
     p.add_argument("--synthetic_len", type=int, default=64, help="items per epoch of the synthetic datasets")

@@ -8,6 +8,7 @@
   * synthetic    SyntheticIM2SDF / SyntheticIM2PointFarthest: generated items, no files needed.
 
   IM2SDF           {'rgb_image' [3,S,S] in [0,1), 'points' [N,3] in [-0.5,0.5), 'values' [N], 'occ' [1,R,R,R] in {0,1}}
+                   ('occ' is float32 as in the reference; uint8 with config.occ_dtype = "uint8")
   IM2PointFarthest {'rgb_image', 'pc' [5000,3]}
 
 The reference's names IM2SDF / IM2PointFarthest pick the file-backed form when the split lists exist under the
@@ -22,11 +23,20 @@ import torch
 from torch.utils import data
 
 
+def _occ_dtype(config):
+    """numpy dtype of the 'occ' item: config.occ_dtype, float32 (the reference's) when it is not set."""
+    name = getattr(config, "occ_dtype", "float32")
+    if name not in ("float32", "uint8"):
+        raise ValueError(f"occ_dtype must be 'float32' or 'uint8' (got {name!r})")
+    return np.dtype(name)
+
+
 class _Base(data.Dataset):
     def __init__(self, config, status="train"):
         self.config, self.status = config, status
         self.datasize = int(getattr(config, "synthetic_len", 64))
         self.img_res = config.img_res
+        self.occ_dtype = _occ_dtype(config)
         self.seed = 333 + (0 if status == "train" else 1)
 
     def __len__(self):
@@ -59,7 +69,7 @@ class SyntheticIM2SDF(_Base):
         shell = np.abs(np.sqrt((gx - centre[0]) ** 2 + (gy - centre[1]) ** 2 + (gz - centre[2]) ** 2)
                        - radius) < (1.0 / self.vox_res)
         return {"rgb_image": self._image(rng), "points": torch.from_numpy(pts),
-                "values": torch.from_numpy(sdf), "occ": torch.from_numpy(shell.astype(np.float32)[None])}
+                "values": torch.from_numpy(sdf), "occ": torch.from_numpy(shell.astype(self.occ_dtype)[None])}
 
     def get_testdata(self, cat_id=None, shape_id=None, cam_id=0):
         item = self[int(cam_id) if cam_id is not None else 0]
@@ -171,6 +181,7 @@ class FileIM2SDF(_FileBase):
     def __init__(self, config, status="train"):
         super().__init__(config, status, max_train_shapes=2000)
         self.vox_res = config.vox_res
+        self.occ_dtype = _occ_dtype(config)
         self.query_samples = np.rint(np.asarray(config.sample_distribution) * config.sample_point_density).astype(np.uint32)
         self.sigmas = config.sigmas
         self._kdtree = None
@@ -224,7 +235,7 @@ class FileIM2SDF(_FileBase):
         f.close()
         return {"rgb_image": self._image(d["rgba_dir"], cam, self.status == "train").float(),
                 "points": torch.from_numpy(samples[:, :3].copy()), "values": torch.from_numpy(samples[:, 3].copy()),
-                "occ": torch.from_numpy(self._occupancy(d["h5_fn"], pc).astype(np.float32))}
+                "occ": torch.from_numpy(self._occupancy(d["h5_fn"], pc).astype(self.occ_dtype))}
 
     def get_testdata(self, cat_id, shape_id, cam_id):
         rgb_dir = os.path.join(self.config.image_dir, cat_id, shape_id, "easy")

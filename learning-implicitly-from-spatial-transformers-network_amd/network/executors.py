@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import chamfer, evaluate, mesh, parallel, refine as RF, utils
+from .. import chamfer, evaluate, mesh, parallel, refine as RF, s2loss, utils
 from . import losses as L
 
 
@@ -68,6 +68,9 @@ class LIST:
         self.query_res = getattr(config, "mcube_znum", None) or config.vox_res
         self.bb_min, self.bb_max, self.vox_res = config.bb_min, config.bb_max, config.vox_res
         self.loss_sdf = L.SDFLoss(self.sdf_scale)
+        self.stage2_loss = getattr(config, "stage2_loss", "torch")
+        if self.stage2_loss not in ("torch", "hip"):
+            raise ValueError(f"stage2_loss must be 'torch' or 'hip' (got {self.stage2_loss!r})")
         # coarse-to-fine grid for test(): --refine_stride 0 is the dense grid
         self.refine_stride = getattr(config, "refine_stride", 0) or None
         self.refine_band = getattr(config, "refine_band", None)
@@ -83,10 +86,17 @@ class LIST:
         occ, sdf_pred = pred
         occ_gt, sdf_gt = gt
         w = 0.9                                     # weighted BCE on the occupancy head (executors.py:138-141)
-        occ_loss = 1000 * (-w * torch.mean(occ_gt * torch.log(occ + 1e-8))
-                           - (1 - w) * torch.mean((1 - occ_gt) * torch.log(1 - occ + 1e-8)))
-        loss = {"occ_loss": occ_loss}
-        loss.update(self.loss_sdf(sdf_pred, sdf_gt))
+        if self.stage2_loss == "hip" and occ.is_cuda:
+            # the local terms in HIP (include/list_s2loss.h): one pass over the volume forward, one backward
+            loss = s2loss.stage2_loss(occ, occ_gt, sdf_pred, sdf_gt, self.sdf_scale, w)
+            occ_loss = loss["occ_loss"]
+        else:
+            if not occ_gt.is_floating_point():      # --occ_dtype uint8 (or a bool volume): the same 0 / 1 in occ's dtype
+                occ_gt = occ_gt.to(occ.dtype)
+            occ_loss = 1000 * (-w * torch.mean(occ_gt * torch.log(occ + 1e-8))
+                               - (1 - w) * torch.mean((1 - occ_gt) * torch.log(1 - occ + 1e-8)))
+            loss = {"occ_loss": occ_loss}
+            loss.update(self.loss_sdf(sdf_pred, sdf_gt))
         rank, world = parallel.world_info()
         if world > 1:
             # One process per GPU holds B_local images.  The reference evaluates SDFLoss over the whole batch
