@@ -107,6 +107,10 @@ def build_parser():
     p.add_argument("--occ_dtype", default="float32", choices=["float32", "uint8"],
                    help="dtype of the occupancy target 'occ' the IM2SDF datasets hand out: uint8 ships a quarter of the "
                         "bytes to the device per step; both losses read it as it is")
+    p.add_argument("--augment", default="host", choices=["host", "hip"],
+                   help="where --random_h_flip / --color_jitter run in training: 'host' in the dataset workers with Pillow; "
+                        "'hip' on the device (augment.py: the file-backed datasets hand out the raw uint8 [H,W,3] image, a "
+                        "quarter of the float32 bytes, and one launch per batch flips, jitters and converts it)")
     p.add_argument("--channels_last", type=_bool, default=True,
                    help="run the encoders that feed the query path in channels-last memory format")
     p.add_argument("--synthetic_len", type=int, default=64, help="items per epoch of the synthetic datasets")

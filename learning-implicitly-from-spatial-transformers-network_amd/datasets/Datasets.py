@@ -10,6 +10,8 @@
   IM2SDF           {'rgb_image' [3,S,S] in [0,1), 'points' [N,3] in [-0.5,0.5), 'values' [N], 'occ' [1,R,R,R] in {0,1}}
                    ('occ' is float32 as in the reference; uint8 with config.occ_dtype = "uint8")
   IM2PointFarthest {'rgb_image', 'pc' [5000,3]}
+                   (with config.augment = "hip" and a training augmentation configured, the file-backed training items
+                   carry 'rgb_image' as the file's uint8 [S,S,3] pixels: the executor augments the batch on the device)
 
 The reference's names IM2SDF / IM2PointFarthest pick the file-backed form when the split lists exist under the
 configured directories and the synthetic one otherwise.  HDF5 needs h5py (not in this image); every `*.h5` path
@@ -128,19 +130,35 @@ def _read_shape_ids(filename):
         return [line.strip("\n") for line in f.readlines()]
 
 
+def _augment_mode(config):
+    """config.augment: 'host' (the dataset augments, as in the reference) when it is not set."""
+    mode = getattr(config, "augment", "host")
+    if mode not in ("host", "hip"):
+        raise ValueError(f"augment must be 'host' or 'hip' (got {mode!r})")
+    return mode
+
+
 def _load_image(fn, config, train, rng):
     """PNG -> float32 [3,H,W] in [0,1], channels as the reference's LIVE reader yields them: PIL
     `Image.open(..).convert('RGB')` followed by T.ToTensor() (Datasets.py:45,213-214,270-271 and :35,171), i.e.
     plane 0 is RED and values are uint8 / 255.  (The cv2 `read_rgba_image` at Datasets.py:300-304 is dead code:
     its call sites at :211 and :269 are commented out.)  Normalize((0,)*3, (1,)*3) is the identity (:171-173).
-    The horizontal flip is applied to the array in training when configured; colour jitter needs torchvision
-    and says so."""
+    In training, when configured: the horizontal flip (a coin from `rng`), then the colour jitter with Pillow's own
+    operations (augment.jitter_pil) and parameters drawn from `rng` (augment.draw_jitter).
+    With config.augment = "hip" a training image that is to be flipped or jittered is returned as it is in the file,
+    uint8 [H,W,3], and nothing is drawn: the executor augments the batch on the device (augment.apply)."""
     from PIL import Image
-    a = np.asarray(Image.open(fn).convert("RGB"), dtype=np.float32) / np.float32(255.0)
-    if train and getattr(config, "random_h_flip", False) and rng.random() < 0.5:
-        a = a[:, ::-1]
-    if train and getattr(config, "color_jitter", False):
-        raise RuntimeError("--color_jitter needs torchvision (ColorJitter(0.3, saturation=0.5, hue=0.5)), not in this image")
+    img = Image.open(fn).convert("RGB")
+    flip = train and getattr(config, "random_h_flip", False)
+    jitter = train and getattr(config, "color_jitter", False)
+    if (flip or jitter) and _augment_mode(config) == "hip":
+        return torch.from_numpy(np.array(img, dtype=np.uint8))
+    if flip and rng.random() < 0.5:
+        img = img.transpose(Image.Transpose.FLIP_LEFT_RIGHT)
+    if jitter:
+        from .. import augment
+        img = augment.jitter_pil(img, augment.draw_jitter(rng))
+    a = np.asarray(img, dtype=np.float32) / np.float32(255.0)
     return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))
 
 
@@ -233,7 +251,7 @@ class FileIM2SDF(_FileBase):
         f = _Arrays(os.path.join(os.path.dirname(d["h5_fn"]), "farthest_pointclouds.h5"))
         pc = f["points_5000"][:]
         f.close()
-        return {"rgb_image": self._image(d["rgba_dir"], cam, self.status == "train").float(),
+        return {"rgb_image": self._image(d["rgba_dir"], cam, self.status == "train"),
                 "points": torch.from_numpy(samples[:, :3].copy()), "values": torch.from_numpy(samples[:, 3].copy()),
                 "occ": torch.from_numpy(self._occupancy(d["h5_fn"], pc).astype(self.occ_dtype))}
 
@@ -257,7 +275,7 @@ class FileIM2PointFarthest(_FileBase):
         f = _Arrays(d["h5_fn"])
         pc = f["points_5000"][:]
         f.close()
-        return {"rgb_image": self._image(d["rgba_dir"], cam, self.status == "train").float(),
+        return {"rgb_image": self._image(d["rgba_dir"], cam, self.status == "train"),
                 "pc": torch.from_numpy(np.asarray(pc, dtype=np.float32))}
 
     def get_testdata(self, cat_id, shape_id, cam_id):

@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import chamfer, evaluate, mesh, parallel, refine as RF, s2loss, utils
+from .. import augment, chamfer, evaluate, mesh, parallel, refine as RF, s2loss, utils
 from . import losses as L
 
 
@@ -19,8 +19,25 @@ def chamfer_distance(x, y):
     return d.min(2)[0].mean(1).mean() + d.min(1)[0].mean(1).mean(), None
 
 
+class _TrainImages:
+    """The 'rgb_image' of a training batch on the device.  A uint8 [B,H,W,3] batch (--augment hip: the datasets hand out
+    the files' pixels) is flipped, jittered and converted there in one launch (augment.apply), with parameters drawn per
+    batch from a generator seeded once per process (per rank); a float batch is copied as it is."""
+
+    def __init__(self, config):
+        self.flip = bool(getattr(config, "random_h_flip", False))
+        self.jitter = bool(getattr(config, "color_jitter", False))
+        self.generator = torch.Generator().manual_seed(333 + parallel.world_info()[0])
+
+    def __call__(self, img, dev):
+        if img.dtype != torch.uint8:
+            return img.to(dev)
+        return augment.apply(img.to(dev), augment.draw_params(img.shape[0], self.flip, self.jitter, self.generator))
+
+
 class CoarseNet:
     def __init__(self, config, model):
+        self.train_images = _TrainImages(config)
         self.loss_fn = chamfer_distance
         self.use_cuda = config.cuda
         self.model = model
@@ -36,7 +53,7 @@ class CoarseNet:
         return next(self.model.parameters()).device
 
     def train(self, batch, calc_loss=True):
-        img, gt = batch["rgb_image"].to(self._device()), batch["pc"].to(self._device())
+        img, gt = self.train_images(batch["rgb_image"], self._device()), batch["pc"].to(self._device())
         pred = self.model(img)
         return pred, {"chamfer_loss": self.calc_loss(pred, gt) if calc_loss else []}
 
@@ -68,6 +85,7 @@ class LIST:
         self.query_res = getattr(config, "mcube_znum", None) or config.vox_res
         self.bb_min, self.bb_max, self.vox_res = config.bb_min, config.bb_max, config.vox_res
         self.loss_sdf = L.SDFLoss(self.sdf_scale)
+        self.train_images = _TrainImages(config)
         self.stage2_loss = getattr(config, "stage2_loss", "torch")
         if self.stage2_loss not in ("torch", "hip"):
             raise ValueError(f"stage2_loss must be 'torch' or 'hip' (got {self.stage2_loss!r})")
@@ -112,7 +130,7 @@ class LIST:
 
     def train(self, batch, calc_loss=True):
         dev = self._device()
-        img, points = batch["rgb_image"].to(dev), batch["points"].to(dev)
+        img, points = self.train_images(batch["rgb_image"], dev), batch["points"].to(dev)
         sdf_gt, occ_gt = batch["values"].to(dev), batch["occ"].to(dev)
         transmat = batch["transmat"].to(dev) if "transmat" in batch else None
         pred = self.model(img, points, transmat)
