@@ -29,6 +29,11 @@ def build_parser():
     p.add_argument("--refine_band", type=float, default=None,
                    help="with --refine_stride: a brick whose corners come within this distance of the iso-level is "
                         "refined (default: the brick's diagonal)")
+    p.add_argument("--mesh_components", type=int, default=0,
+                   help="keep only the K connected components of the predicted mesh with the most faces "
+                        "(components.py, on the device, before export and --eval_pred); 0 keeps all")
+    p.add_argument("--mesh_min_faces", type=int, default=0,
+                   help="drop the connected components of the predicted mesh with fewer faces than this; 0 drops none")
     p.add_argument("--save_volume", action="store_true",
                    help="test.py: also write each item's raw SDF volume (<stem>_sdf.npy) next to its mesh")
     p.add_argument("--chunk_s", type=int, default=0)

@@ -223,6 +223,15 @@ class Mesh:
             raise ValueError(f"{path}: export writes .obj or .ply")
         return path
 
+    def keep_components(self, keep="all", min_faces=0, return_info=False):
+        """A new Mesh of the components components.select_components keeps (the `keep` with the most faces, of those
+        with at least `min_faces`), vertices and faces in their order, on the host (components.keep_components_cpu);
+        with return_info also its info dict."""
+        from . import components
+        v, f, info = components.keep_components_cpu(self.vertices, self.faces, keep, min_faces)
+        m = Mesh(v, f)
+        return (m, info) if return_info else m
+
     def to_trimesh(self):
         import trimesh
         return trimesh.Trimesh(self.vertices, self.faces, process=False)

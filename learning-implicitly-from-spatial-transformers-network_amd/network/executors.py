@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import augment, chamfer, evaluate, mesh, parallel, refine as RF, s2loss, utils
+from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, s2loss, utils
 from . import losses as L
 
 
@@ -93,6 +93,13 @@ class LIST:
         self.refine_stride = getattr(config, "refine_stride", 0) or None
         self.refine_band = getattr(config, "refine_band", None)
         self.last_grid_stats = None
+        # --mesh_components K / --mesh_min_faces N: filter the predicted mesh's components; 0 / 0 filters nothing
+        self.mesh_components = int(getattr(config, "mesh_components", 0) or 0)
+        self.mesh_min_faces = int(getattr(config, "mesh_min_faces", 0) or 0)
+        if self.mesh_components < 0 or self.mesh_min_faces < 0:
+            raise ValueError(f"mesh_components and mesh_min_faces must be >= 0 (got {self.mesh_components}, "
+                             f"{self.mesh_min_faces})")
+        self.last_components = None
 
     def _device(self):
         return self.device or next(self.model.parameters()).device
@@ -207,9 +214,19 @@ class LIST:
         volume, occ, vox_feat = (self.predict_grid(img, transmat, refine=self.refine_stride, band=self.refine_band)
                                  if self.refine_stride else self.predict_grid(img, transmat))
         # marching cubes on the device, where the volume lies (mesh.marching_cubes: mcubes' surface of -volume at 0)
-        pred_mesh = mesh.Mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5))
+        pred_mesh = mesh.Mesh(*self.filter_mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5)))
         score = self.eval(pred_mesh, batch.get("gt_mesh")) if eval_pred else {}
         return [pred_mesh, occ, vox_feat[0].squeeze(1)], score
+
+    def filter_mesh(self, verts, faces):
+        """The mesh as marching_cubes left it on the device, without the components --mesh_components /
+        --mesh_min_faces drop (components.keep_components; its info lands in self.last_components).  With both at 0
+        the tensors come back untouched."""
+        if not (self.mesh_components or self.mesh_min_faces):
+            return verts, faces
+        verts, faces, self.last_components = components.keep_components(
+            verts, faces, keep=self.mesh_components or "all", min_faces=self.mesh_min_faces)
+        return verts, faces
 
     def eval(self, pred, gt):
         """eval_util.py:eval_mesh of the predicted mesh against the ground truth (a Mesh or a path to one), on the

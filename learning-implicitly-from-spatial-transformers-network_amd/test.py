@@ -95,10 +95,14 @@ def test_all(config, save_volume=None, eval_pred=None):
             if save_volume:
                 np.save(stem + "_sdf.npy", volume.cpu().numpy())
             t0 = time.time()
-            m = mesh.Mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5))
+            executor.last_components = None
+            m = mesh.Mesh(*executor.filter_mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5)))
             dt = time.time() - t0
             m.export(stem + "_pred.obj")
             print(f"  mesh: {len(m.vertices)} vertices, {len(m.faces)} faces in {dt * 1e3:.1f} ms -> {stem}_pred.obj")
+            cc = executor.last_components
+            if cc is not None:
+                print(f"  components: {cc['K']} found, {len(cc['kept'])} kept, {cc['dropped_faces']} faces dropped")
             if eval_pred:
                 gt = batch.get("gt_mesh")
                 if gt is None:

@@ -26,7 +26,7 @@ def main():
     for m, nice in zip(re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S), dem):
         body = m.group(2)
         g = lambda k: (re.search(r"\.amdhsa_" + k + r" (\d+)", body) or [0, "?"])[1]
-        nice = re.sub(r"^void list::", "", nice)
+        nice = re.sub(r"^(void )?(list::|\(anonymous namespace\)::)?", "", nice)
         nice = re.sub(r"\(.*$", "", nice)
         print(f"{nice:48s} vgpr {g('next_free_vgpr'):>4s} (arch {g('accum_offset'):>3s})  sgpr {g('next_free_sgpr'):>3s}"
               f"  lds {g('group_segment_fixed_size'):>6s}  scratch {g('private_segment_fixed_size'):>4s}")
