@@ -34,6 +34,12 @@ def build_parser():
                         "(components.py, on the device, before export and --eval_pred); 0 keeps all")
     p.add_argument("--mesh_min_faces", type=int, default=0,
                    help="drop the connected components of the predicted mesh with fewer faces than this; 0 drops none")
+    p.add_argument("--render_pred", default="none", choices=["none", "view", "canonical", "both"],
+                   help="pictures of the predicted mesh beside its _pred.obj (render.py, on the device): 'view' from the "
+                        "model's own camera (the predicted or given trans_mat) over the input image (_pred_view.png), "
+                        "'canonical' three orthographic views along the array axes (_pred_x.png, _pred_y.png, _pred_z.png), "
+                        "'both'; 'none' renders nothing")
+    p.add_argument("--render_size", type=int, default=0, help="side of the rendered pictures in pixels (0: --img_res)")
     p.add_argument("--save_volume", action="store_true",
                    help="test.py: also write each item's raw SDF volume (<stem>_sdf.npy) next to its mesh")
     p.add_argument("--chunk_s", type=int, default=0)

@@ -190,9 +190,15 @@ def marching_cubes_cpu(volume, level=0.0, bb_min=-0.5, bb_max=0.5):
 
 # ---- mesh -----------------------------------------------------------------------------------------------------------
 class Mesh:
-    """vertices float32 [V,3] and faces int32 [F,3] (0-based) on the host."""
+    """vertices float32 [V,3] and faces int32 [F,3] (0-based) on the host.  Made from CUDA tensors (as marching_cubes
+    and components.keep_components return them) it also keeps those, for render()."""
 
     def __init__(self, vertices, faces):
+        self._device = None
+        if getattr(vertices, "is_cuda", False) and getattr(faces, "is_cuda", False):
+            import torch
+            self._device = (vertices.detach().to(torch.float32).reshape(-1, 3).contiguous(),
+                            faces.detach().to(torch.int32).reshape(-1, 3).contiguous())
         if hasattr(vertices, "detach"):
             vertices = vertices.detach().cpu().numpy()
         if hasattr(faces, "detach"):
@@ -231,6 +237,20 @@ class Mesh:
         v, f, info = components.keep_components_cpu(self.vertices, self.faces, keep, min_faces)
         m = Mesh(v, f)
         return (m, info) if return_info else m
+
+    def render(self, camera, H, W, mode="lambert", background=None, alpha=1.0):
+        """A picture of the mesh from `camera` (render.Camera) -> uint8 [H,W,3] on the host: render.rasterize + shade, in
+        HIP on the device the mesh was made on, else in numpy.  mode: "lambert" (head-light grey) or "normal"; background:
+        uint8 [H,W,3] (array or tensor; white when None); alpha: the mesh's opacity over it."""
+        from . import render as R
+        if self._device is not None:
+            v, f = self._device
+            if background is not None:
+                import torch
+                background = torch.as_tensor(np.asarray(background.detach().cpu() if hasattr(background, "detach")
+                                                        else background, dtype=np.uint8)).contiguous().to(v.device)
+            return R.render(v, f, camera, H, W, mode, background, alpha).cpu().numpy()
+        return R.render(self.vertices, self.faces, camera, H, W, mode, background, alpha)
 
     def to_trimesh(self):
         import trimesh

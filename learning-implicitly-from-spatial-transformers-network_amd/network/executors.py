@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, s2loss, utils
+from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, render, s2loss, utils
 from . import losses as L
 
 
@@ -33,6 +33,11 @@ class _TrainImages:
         if img.dtype != torch.uint8:
             return img.to(dev)
         return augment.apply(img.to(dev), augment.draw_params(img.shape[0], self.flip, self.jitter, self.generator))
+
+
+# --render_pred -> (the model's own view, the three canonical views)
+RENDER_VIEWS = {"none": (False, False), "view": (True, False), "canonical": (False, True), "both": (True, True)}
+VIEW_ALPHA = 0.65            # the mesh's opacity over the input image in the "view" picture
 
 
 class CoarseNet:
@@ -100,6 +105,12 @@ class LIST:
             raise ValueError(f"mesh_components and mesh_min_faces must be >= 0 (got {self.mesh_components}, "
                              f"{self.mesh_min_faces})")
         self.last_components = None
+        # --render_pred: pictures of the predicted mesh (render.py); 'none' renders nothing
+        self.render_pred = getattr(config, "render_pred", "none") or "none"
+        if self.render_pred not in RENDER_VIEWS:
+            raise ValueError(f"render_pred must be one of {sorted(RENDER_VIEWS)} (got {self.render_pred!r})")
+        self.render_size = int(getattr(config, "render_size", 0) or 0) or int(getattr(config, "img_res", 224))
+        self.last_transmat = None                   # the camera predict_grid used ([B,4,3]): given, or predicted
 
     def _device(self):
         return self.device or next(self.model.parameters()).device
@@ -162,6 +173,7 @@ class LIST:
         dev = img.device
         res = res or self.query_res
         feat_l2, vox_feat, transmat, _, occ = net.encode(img, transmat)
+        self.last_transmat = transmat
         total = res ** 3
         rank, world = parallel.world_info() if shard else (0, 1)
         if world > 1:        # every rank samples rank 0's maps: sharded == unsharded bit for bit (parallel.py)
@@ -192,6 +204,7 @@ class LIST:
         dev = img.device
         res = res or self.query_res
         feat_l2, vox_feat, transmat, _, occ = net.encode(img, transmat)
+        self.last_transmat = transmat
         rank, world = parallel.world_info() if shard else (0, 1)
         if world > 1:        # as the dense grid: every rank samples rank 0's maps
             parallel.broadcast_from_rank0(list(feat_l2) + list(vox_feat) + [transmat, occ])
@@ -235,5 +248,45 @@ class LIST:
             raise ValueError("LIST.eval: no ground-truth mesh (the batch carries no 'gt_mesh')")
         return evaluate.eval_mesh(pred, gt, self.bb_min, self.bb_max, device=self._device())
 
+    def render_views(self, batch, pred, which=None):
+        """Pictures of the predicted mesh (pred: test()'s list, or the Mesh) -> {name: uint8 [S,S,3]}, S = --render_size.
+        "view": the mesh from the camera predict_grid used (self.last_transmat; else the batch's 'transmat'), head-light
+        grey at VIEW_ALPHA over the input image resized to S x S -- where the network sampled the image, is the shape on
+        the object?  "x", "y", "z": orthographic head-light views along array axis 0, 1, 2 of the volume.  which: 'view',
+        'canonical' or 'both' (default: --render_pred, 'both' when that is 'none').  Without a camera there is no "view";
+        a mesh without a valid face gives the background."""
+        m = pred[0] if isinstance(pred, (list, tuple)) else pred
+        which = which or (self.render_pred if self.render_pred != "none" else "both")
+        S = self.render_size
+        out = {}
+        tm = self.last_transmat if self.last_transmat is not None else batch.get("transmat")
+        if RENDER_VIEWS[which][0] and tm is not None:
+            if hasattr(tm, "detach"):
+                tm = tm.detach().float().cpu().numpy()
+            net = _unwrap(self.model)
+            map_size = getattr(getattr(net, "percep_pooling", None), "map_size", 137)
+            cam = render.Camera.from_transmat(np.asarray(tm, dtype=np.float32).reshape(-1, 4, 3)[0], map_size)
+            out["view"] = m.render(cam, S, S, "lambert", self._input_image(batch, S), VIEW_ALPHA)
+        if RENDER_VIEWS[which][1]:
+            for axis, name in enumerate("xyz"):
+                cam = render.Camera.orthographic(axis, S, S, self.bb_min, self.bb_max)
+                out[name] = m.render(cam, S, S, "lambert")
+        return out
+
+    @staticmethod
+    def _input_image(batch, S):
+        """The batch's first 'rgb_image' ([B,3,H,W] or [3,H,W], values in [0,1]) as uint8 [S,S,3]; None without one."""
+        img = batch.get("rgb_image")
+        if img is None:
+            return None
+        img = torch.as_tensor(img).detach().float().cpu()
+        img = img[0] if img.dim() == 4 else img
+        if img.shape[-2:] != (S, S):
+            img = torch.nn.functional.interpolate(img[None], size=(S, S), mode="bilinear", align_corners=False)[0]
+        return (img.clamp(0, 1) * 255 + 0.5).to(torch.uint8).permute(1, 2, 0).contiguous().numpy()
+
     def save(self, batch, pred, fname):
         pred[0].export(fname + "_pred.obj")
+        if self.render_pred != "none":
+            for name, img in self.render_views(batch, pred).items():
+                render.save_png(f"{fname}_pred_{name}.png", img)

@@ -9,7 +9,9 @@ query grid with the HIP path and extract the iso-surface on the GPU (mesh.marchi
 
 `--refine_stride s` (2, 4, 8) queries the coarse-to-fine grid of refine.py instead of every grid point: the stride-s
 lattice and the fine points near the surface, the rest interpolated (`--refine_band` sets how near).  `--save_volume`
-also writes the [res,res,res] SDF volume (<stem>_sdf.npy; with --refine_stride the filled one).  `--eval_pred` scores
+also writes the [res,res,res] SDF volume (<stem>_sdf.npy; with --refine_stride the filled one).  `--render_pred view|canonical|both`
+renders the mesh on the device (render.py) from the model's own camera over the input image (<stem>_pred_view.png) and / or
+along the three array axes (<stem>_pred_x.png, _y, _z), at `--render_size` pixels a side.  `--eval_pred` scores
 every item whose dataset gives a ground-truth mesh (evaluate.eval_mesh on the device: Chamfer-L2, precision / recall / F-score, IoU) and
 writes <results_dir>test_objs/<cat>.csv, one row per item and a final `Mean` row, as the reference does; items without
 one (the synthetic datasets) are reported as skipped."""
@@ -21,7 +23,7 @@ import time
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(_HERE))
 import list_amd                                          # noqa: E402
-from list_amd import arguments, evaluate, mesh, utils   # noqa: E402
+from list_amd import arguments, evaluate, mesh, render, utils   # noqa: E402
 from list_amd.train import wrap_model                   # noqa: E402
 
 import numpy as np                                       # noqa: E402
@@ -100,6 +102,13 @@ def test_all(config, save_volume=None, eval_pred=None):
             dt = time.time() - t0
             m.export(stem + "_pred.obj")
             print(f"  mesh: {len(m.vertices)} vertices, {len(m.faces)} faces in {dt * 1e3:.1f} ms -> {stem}_pred.obj")
+            if getattr(config, "render_pred", "none") != "none":
+                t0 = time.time()
+                views = executor.render_views(batch, m)
+                for name, img in views.items():
+                    render.save_png(f"{stem}_pred_{name}.png", img)
+                print(f"  rendered {', '.join(views)} at {executor.render_size}^2 in {(time.time() - t0) * 1e3:.1f} ms "
+                      f"-> {stem}_pred_<view>.png")
             cc = executor.last_components
             if cc is not None:
                 print(f"  components: {cc['K']} found, {len(cc['kept'])} kept, {cc['dropped_faces']} faces dropped")
