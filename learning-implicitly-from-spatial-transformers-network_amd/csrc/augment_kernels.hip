@@ -143,15 +143,13 @@ int list_augment_fwd(const uint8_t* src, float* dst, int64_t B, int64_t H, int64
   const dim3 grid((unsigned)cdiv(H * Wq, kThreads), (unsigned)B), block(kThreads);
   const bool vec = W % kCols == 0 && !misaligned(src, 4) && !misaligned(dst, 16);
   hipStream_t s = (hipStream_t)stream;
-  if (vec && channels_last)
-    hipLaunchKernelGGL((augment_kernel<true, true>), grid, block, 0, s, src, dst, (int)H, (int)W, Wq, params_device);
-  else if (vec)
-    hipLaunchKernelGGL((augment_kernel<true, false>), grid, block, 0, s, src, dst, (int)H, (int)W, Wq, params_device);
-  else if (channels_last)
-    hipLaunchKernelGGL((augment_kernel<false, true>), grid, block, 0, s, src, dst, (int)H, (int)W, Wq, params_device);
-  else
-    hipLaunchKernelGGL((augment_kernel<false, false>), grid, block, 0, s, src, dst, (int)H, (int)W, Wq, params_device);
-  return launched("augment_kernel");
+  auto run = [&](auto kernel) {
+    return launch("augment_kernel", kernel, grid, block, s, src, dst, (int)H, (int)W, Wq, params_device);
+  };
+  if (vec && channels_last) return run(augment_kernel<true, true>);
+  if (vec) return run(augment_kernel<true, false>);
+  if (channels_last) return run(augment_kernel<false, true>);
+  return run(augment_kernel<false, false>);
 }
 
 int list_augment_pixel(const uint8_t* rgb_in, const ListAugmentParams* p, uint8_t* rgb_out, float* out) {

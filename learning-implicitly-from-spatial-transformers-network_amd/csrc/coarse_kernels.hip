@@ -48,28 +48,28 @@ int cam_out(const ListCoarseShape& s, int k) { return k == 2 ? 12 : s.hidden; }
 
 PackedLayout packed_layout(const ListCoarseShape& s) {
   PackedLayout p = {};
-  size_t o = 0;
-  auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4); return r; };
+  Carver c;
+  auto f32 = [&](size_t n) { return c.take(n * sizeof(float)); };
   const int L = s.n_degrees;
   for (int l = 0; l < L; ++l) {
-    for (int i = 0; i <= l; ++i) p.root[l][i] = take((size_t)s.features[i] * s.features[l + 1]);
-    p.wc[l] = take((size_t)s.features[l] * s.features[l + 1]);
-    if (s.activation[l]) p.bias[l] = take((size_t)s.degrees[l] * s.features[l + 1]);
+    for (int i = 0; i <= l; ++i) p.root[l][i] = f32((size_t)s.features[i] * s.features[l + 1]);
+    p.wc[l] = f32((size_t)s.features[l] * s.features[l + 1]);
+    if (s.activation[l]) p.bias[l] = f32((size_t)s.degrees[l] * s.features[l + 1]);
   }
   if (s.has_mlp)
     for (int k = 0; k < 3; ++k) {
-      p.mlp_w[k] = take((size_t)mlp_width(k) * mlp_width(k + 1));
-      p.mlp_b[k] = take(mlp_width(k + 1));
-      p.mlp_s[k] = take(mlp_width(k + 1));
-      p.mlp_t[k] = take(mlp_width(k + 1));
+      p.mlp_w[k] = f32((size_t)mlp_width(k) * mlp_width(k + 1));
+      p.mlp_b[k] = f32(mlp_width(k + 1));
+      p.mlp_s[k] = f32(mlp_width(k + 1));
+      p.mlp_t[k] = f32(mlp_width(k + 1));
     }
   if (s.has_camera)
     for (int k = 0; k < 3; ++k) {
-      p.cam_w[k] = take((size_t)cam_in(s, k) * cam_out(s, k));
-      p.cam_b[k] = take(cam_out(s, k));
-      if (k < 2) { p.cam_s[k] = take(cam_out(s, k)); p.cam_t[k] = take(cam_out(s, k)); }
+      p.cam_w[k] = f32((size_t)cam_in(s, k) * cam_out(s, k));
+      p.cam_b[k] = f32(cam_out(s, k));
+      if (k < 2) { p.cam_s[k] = f32(cam_out(s, k)); p.cam_t[k] = f32(cam_out(s, k)); }
     }
-  p.total = o;
+  p.total = c.total();
   return p;
 }
 
@@ -83,12 +83,11 @@ struct WorkspaceLayout { size_t level[kMaxL], tile_max, total; };
 
 WorkspaceLayout workspace_layout(const ListCoarseShape& s, int B) {
   WorkspaceLayout w = {};
-  size_t o = 0;
-  auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4); return r; };
+  Carver c;
   const int L = s.n_degrees;
-  for (int l = 1; l < L; ++l) w.level[l] = take((size_t)B * nodes_of(s, l) * s.features[l]);
-  if (s.has_mlp) w.tile_max = take((size_t)B * cdiv(nodes_of(s, L), kTile) * kCode);
-  w.total = o ? o : 256;
+  for (int l = 1; l < L; ++l) w.level[l] = c.take((size_t)B * nodes_of(s, l) * s.features[l] * sizeof(float));
+  if (s.has_mlp) w.tile_max = c.take((size_t)B * cdiv(nodes_of(s, L), kTile) * kCode * sizeof(float));
+  w.total = c.total() ? c.total() : 256;
   return w;
 }
 
@@ -228,15 +227,16 @@ __global__ __launch_bounds__(kThreads) void coarse_tree_kernel(TreeArgs a) {
   }
 }
 
-hipError_t launch_tree(const TreeArgs& a, hipStream_t s) {
+// (a launch error of the forward is reported under the entry point's name, not the kernel's)
+int launch_tree(const TreeArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)((int64_t)a.node * a.deg), (unsigned)cdiv(a.B, kGroup));
   const int nb = a.B < kGroup ? a.B : kGroup;
-  if (nb <= 1) hipLaunchKernelGGL(coarse_tree_kernel<1>, grid, dim3(kThreads), 0, s, a);
-  else if (nb <= 2) hipLaunchKernelGGL(coarse_tree_kernel<2>, grid, dim3(kThreads), 0, s, a);
-  else if (nb <= 4) hipLaunchKernelGGL(coarse_tree_kernel<4>, grid, dim3(kThreads), 0, s, a);
-  else if (nb <= 8) hipLaunchKernelGGL(coarse_tree_kernel<8>, grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL(coarse_tree_kernel<16>, grid, dim3(kThreads), 0, s, a);
-  return hipGetLastError();
+  auto run = [&](auto kernel) { return launch("list_coarse_forward", kernel, grid, dim3(kThreads), s, a); };
+  if (nb <= 1) return run(coarse_tree_kernel<1>);
+  if (nb <= 2) return run(coarse_tree_kernel<2>);
+  if (nb <= 4) return run(coarse_tree_kernel<4>);
+  if (nb <= 8) return run(coarse_tree_kernel<8>);
+  return run(coarse_tree_kernel<16>);
 }
 
 // ---- point MLP -------------------------------------------------------------------------------------------------------
@@ -426,8 +426,6 @@ __global__ void coarse_mark_kernel(const float* __restrict__ pc, float* __restri
   occ[((b * R + ix) * R + iy) * (int64_t)R + iz] = 1.0f;
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)cdiv(n, kThreads); }
-
 }  // namespace
 
 extern "C" {
@@ -474,10 +472,11 @@ int list_coarse_prep_weights(const ListCoarseShape* shape, const ListCoarseParam
         return fail(LIST_ERR_ARG, "list_coarse_prep_weights: a camera array of layer %d is NULL", k);
 
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)packed;
+  int rc = LIST_OK;                    // of the first launch that failed; nothing is launched after it
   auto put = [&](const float* src, size_t off, int rows, int cols, int transpose) {
-    hipLaunchKernelGGL(coarse_pack_kernel, dim3(blocks_for((int64_t)rows * cols)), dim3(kThreads), 0, s, src,
-                       (float*)(base + off), rows, cols, transpose);
+    if (rc == LIST_OK)
+      rc = launch("list_coarse_prep_weights", coarse_pack_kernel, dim3(blocks_for((int64_t)rows * cols, kThreads)),
+                  dim3(kThreads), s, src, at<float>(packed, off), rows, cols, transpose);
   };
   for (int l = 0; l < L; ++l) {
     const int out = S.features[l + 1];
@@ -502,7 +501,7 @@ int list_coarse_prep_weights(const ListCoarseShape* shape, const ListCoarseParam
         put(params->cam_t[k], P.cam_t[k], 1, cam_out(S, k), 0);
       }
     }
-  return launched("list_coarse_prep_weights");
+  return rc;
 }
 
 int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* io, int32_t step_begin,
@@ -541,21 +540,22 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
   if (int rc = check_step_range("list_coarse_forward_steps", step_begin, step_end, n_steps_of(S))) return rc;
 
   hipStream_t s = (hipStream_t)stream;
-  const char* pk = (const char*)A.packed;
-  char* ws = (char*)A.workspace;
-  auto f = [&](size_t off) { return (const float*)(pk + off); };
+  const void* pk = A.packed;
+  void* ws = A.workspace;
+  auto f = [&](size_t off) { return at<float>(pk, off); };
   const int B = A.B;
   const int64_t Pn = nodes_of(S, L);
   const int tiles = (int)cdiv(Pn, kTile);
-  float* tile_max = (float*)(ws + W.tile_max);
+  float* tile_max = at<float>(ws, W.tile_max);
+  const char* const name = "list_coarse_forward";      // a launch error is reported under the entry point's name
 
   for (int step = step_begin; step < step_end; ++step) {
-    hipError_t e = hipSuccess;
+    int rc = LIST_OK;
     if (step < L) {
       const int l = step;
       TreeArgs t = {};
       for (int i = 0; i <= l; ++i) {
-        t.level[i] = i == 0 ? A.feat_g : (const float*)(ws + W.level[i]);
+        t.level[i] = i == 0 ? A.feat_g : at<float>(ws, W.level[i]);
         t.rootT[i] = f(P.root[l][i]);
         t.nodes[i] = (int32_t)nodes_of(S, i);
         t.feat[i] = S.features[i];
@@ -563,10 +563,10 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
       t.wcT = f(P.wc[l]);
       t.bias = S.activation[l] ? f(P.bias[l]) : nullptr;
       t.w_branch = A.w_branch[l];
-      t.out = l == L - 1 ? A.pc : (float*)(ws + W.level[l + 1]);
+      t.out = l == L - 1 ? A.pc : at<float>(ws, W.level[l + 1]);
       t.depth = l, t.node = (int32_t)nodes_of(S, l), t.in = S.features[l], t.out_f = S.features[l + 1];
       t.deg = S.degrees[l], t.B = B;
-      e = launch_tree(t, s);
+      rc = launch_tree(t, s);
     } else if (step == L) {
       if (!A.coarse) continue;
       MlpArgs m = {A.pc,
@@ -574,12 +574,10 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
                    f(P.mlp_w[1]), f(P.mlp_b[1]), f(P.mlp_s[1]), f(P.mlp_t[1]),
                    f(P.mlp_w[2]), f(P.mlp_b[2]), f(P.mlp_s[2]), f(P.mlp_t[2]),
                    tile_max, (int32_t)Pn, tiles};
-      hipLaunchKernelGGL(coarse_mlp_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kThreads), 0, s, m);
-      e = hipGetLastError();
+      rc = launch(name, coarse_mlp_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kThreads), s, m);
     } else if (step == L + 1) {
       if (!A.coarse) continue;
-      hipLaunchKernelGGL(coarse_max_kernel, dim3((unsigned)B), dim3(kCode), 0, s, (const float*)tile_max, A.coarse, tiles);
-      e = hipGetLastError();
+      rc = launch(name, coarse_max_kernel, dim3((unsigned)B), dim3(kCode), s, tile_max, A.coarse, tiles);
     } else if (step == L + 2) {
       if (!camera) continue;
       CameraArgs c = {};
@@ -587,24 +585,22 @@ int list_coarse_forward_steps(const ListCoarseShape* shape, const ListCoarseIO* 
       for (int k = 0; k < 3; ++k) c.wT[k] = f(P.cam_w[k]), c.b[k] = f(P.cam_b[k]);
       for (int k = 0; k < 2; ++k) c.s[k] = f(P.cam_s[k]), c.t[k] = f(P.cam_t[k]);
       c.trans_mat = A.trans_mat, c.g2 = S.g2, c.hidden = S.hidden;
-      hipLaunchKernelGGL(coarse_camera_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, c);
-      e = hipGetLastError();
+      rc = launch(name, coarse_camera_kernel, dim3((unsigned)B), dim3(kThreads), s, c);
     } else if (step == L + 3) {
       if (!A.occ) continue;
       const int64_t n = (int64_t)B * A.R * A.R * A.R;
       // a tensor's storage is 16-byte aligned where an allocator made it; a view that is not is cleared by floats
       const int64_t n4 = misaligned(A.occ, 16) ? 0 : n / 4;
       const int64_t work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
-      hipLaunchKernelGGL(coarse_clear_kernel, dim3(blocks_for(work)), dim3(kThreads), 0, s, (float4*)A.occ, n4, A.occ, n);
-      e = hipGetLastError();
+      rc = launch(name, coarse_clear_kernel, dim3(blocks_for(work, kThreads)), dim3(kThreads), s, (float4*)A.occ, n4,
+                  A.occ, n);
     } else {
       if (!A.occ) continue;
       const int64_t BP = (int64_t)B * Pn;
-      hipLaunchKernelGGL(coarse_mark_kernel, dim3(blocks_for(BP)), dim3(kThreads), 0, s, (const float*)A.pc, A.occ, BP,
-                         (int)Pn, (int)A.R, A.bb_min, A.bb_extent);
-      e = hipGetLastError();
+      rc = launch(name, coarse_mark_kernel, dim3(blocks_for(BP, kThreads)), dim3(kThreads), s, A.pc, A.occ, BP, (int)Pn,
+                  (int)A.R, A.bb_min, A.bb_extent);
     }
-    if (e != hipSuccess) return hip_fail(e, "list_coarse_forward");
+    if (rc) return rc;
   }
   return LIST_OK;
 }

@@ -16,9 +16,9 @@
 // however stale a read is.  Nothing here waits for another thread; the kernel boundaries are the only synchronisation
 // (DESIGN section 19 has the argument for the stopping rule).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include "list_components.h"
+#include "list_cub.h"
 #include "list_host.h"
 
 namespace {
@@ -296,24 +296,24 @@ int check_sizes(int64_t V, int64_t F) {
   return LIST_OK;
 }
 
+// the layout, or false with the refusal's message set
 bool layout(int64_t V, int64_t F, Layout* L) {
-  size_t sv = 0, sf = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, sv, (const int32_t*)nullptr, (int32_t*)nullptr, (int)V) != hipSuccess ||
-      hipcub::DeviceScan::ExclusiveSum(nullptr, sf, (const int32_t*)nullptr, (int32_t*)nullptr, (int)F) != hipSuccess)
-    return false;
-  const size_t nv = align_up((size_t)V * sizeof(int32_t)), nf = align_up((size_t)F * sizeof(int32_t));
-  L->parent = 0;
-  L->fcount = L->parent + nv;
-  L->vcount = L->fcount + nv;
-  L->vflag = L->vcount + nv;
-  L->vscan = L->vflag + nv;
-  L->fflag = L->vscan + nv;
-  L->fscan = L->fflag + nf;
-  L->used = L->fscan + nf;
-  L->invalid = L->used + align_up((size_t)V);
-  L->scratch = L->invalid + align_up(sizeof(int32_t));
+  size_t sv, sf;
+  if (!exclusive_sum_scratch<int32_t>(V, &sv) || !exclusive_sum_scratch<int32_t>(F, &sf)) return false;
+  const size_t nv = (size_t)V * sizeof(int32_t), nf = (size_t)F * sizeof(int32_t);
+  Carver c;
+  L->parent = c.take(nv);
+  L->fcount = c.take(nv);
+  L->vcount = c.take(nv);
+  L->vflag = c.take(nv);
+  L->vscan = c.take(nv);
+  L->fflag = c.take(nf);
+  L->fscan = c.take(nf);
+  L->used = c.take((size_t)V);
+  L->invalid = c.take(sizeof(int32_t));
   L->scratch_bytes = sv > sf ? sv : sf;
-  L->total = L->scratch + align_up(L->scratch_bytes);
+  L->scratch = c.take(L->scratch_bytes);
+  L->total = c.total();
   return true;
 }
 
@@ -326,17 +326,19 @@ int check_mesh(int64_t V, int64_t F, const void* faces, const void* workspace) {
 
 // the workspace: checked last (its size comes from hipCUB, which asks the device)
 int check_workspace(int64_t V, int64_t F, size_t workspace_bytes, Layout* L) {
-  if (!layout(V, F, L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
+  if (!layout(V, F, L)) return LIST_ERR_HIP;
   if (workspace_bytes < L->total) return workspace_too_small(workspace_bytes, L->total, "list_cc_workspace_bytes");
   return LIST_OK;
 }
 
-unsigned blocks(int64_t n) { return (unsigned)(n < 1 ? 1 : (cdiv(n, kThreads) < kMaxBlocks ? cdiv(n, kThreads) : kMaxBlocks)); }
+// Every kernel here strides over its n items on the same capped grid
+template <typename K, typename... Args>
+int run(const char* name, K kernel, int64_t n, hipStream_t s, Args... args) {
+  return launch(name, kernel, dim3(blocks_capped(n, kThreads, kMaxBlocks)), dim3(kThreads), s, args...);
+}
 
-int scan(char* ws, const Layout& L, const int32_t* in, int32_t* out, int64_t n, hipStream_t s) {
-  size_t scratch = L.scratch_bytes;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, in, out, (int)n, s);
-  return e == hipSuccess ? LIST_OK : hip_fail(e, "hipcub::DeviceScan::ExclusiveSum");
+int scan(void* ws, const Layout& L, const int32_t* in, int32_t* out, int64_t n, hipStream_t s) {
+  return exclusive_sum(at<char>(ws, L.scratch), L.scratch_bytes, in, out, n, s);
 }
 
 }  // namespace
@@ -346,13 +348,8 @@ extern "C" {
 const char* list_cc_last_error(void) { return g_err; }
 
 size_t list_cc_workspace_bytes(int64_t V, int64_t F) {
-  if (check_sizes(V, F) != LIST_OK) return 0;
   Layout L;
-  if (!layout(V, F, &L)) {
-    fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-    return 0;
-  }
-  return L.total;
+  return check_sizes(V, F) == LIST_OK && layout(V, F, &L) ? L.total : 0;
 }
 
 int list_cc_begin(const int32_t* faces, int64_t V, int64_t F, void* workspace, size_t workspace_bytes, void* stream) {
@@ -361,14 +358,12 @@ int list_cc_begin(const int32_t* faces, int64_t V, int64_t F, void* workspace, s
   if (int rc = check_workspace(V, F, workspace_bytes, &L)) return rc;
   if (V == 0 || F == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  int32_t* invalid = (int32_t*)(ws + L.invalid);
-  uint8_t* used = (uint8_t*)(ws + L.used);
-  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, (int32_t*)(ws + L.parent), used,
-                     (int32_t*)(ws + L.fcount), (int32_t*)(ws + L.vcount), invalid);
-  if (int rc = launched("cc_init_kernel")) return rc;
-  hipLaunchKernelGGL(cc_mark_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, faces, F, (uint32_t)V, used, invalid);
-  return launched("cc_mark_kernel");
+  int32_t* invalid = at<int32_t>(workspace, L.invalid);
+  uint8_t* used = at<uint8_t>(workspace, L.used);
+  if (int rc = run("cc_init_kernel", cc_init_kernel, V, s, V, at<int32_t>(workspace, L.parent), used,
+                   at<int32_t>(workspace, L.fcount), at<int32_t>(workspace, L.vcount), invalid))
+    return rc;
+  return run("cc_mark_kernel", cc_mark_kernel, F, s, faces, F, (uint32_t)V, used, invalid);
 }
 
 int list_cc_rounds(const int32_t* faces, int64_t V, int64_t F, void* workspace, size_t workspace_bytes,
@@ -385,13 +380,12 @@ int list_cc_rounds(const int32_t* faces, int64_t V, int64_t F, void* workspace, 
   const hipError_t e = hipMemsetAsync(changed, 0, (size_t)n_rounds * sizeof(int32_t), s);
   if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(changed)");
   if (V == 0 || F == 0) return LIST_OK;
-  int32_t* parent = (int32_t*)((char*)workspace + L.parent);
+  int32_t* parent = at<int32_t>(workspace, L.parent);
   for (int r = 0; r < n_rounds; ++r) {
-    hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, faces, F, (uint32_t)V, parent,
-                       r ? changed + r - 1 : (const int32_t*)nullptr, changed + r);
-    if (int rc = launched("cc_hook_kernel")) return rc;
-    hipLaunchKernelGGL(cc_compress_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, parent, changed + r);
-    if (int rc = launched("cc_compress_kernel")) return rc;
+    if (int rc = run("cc_hook_kernel", cc_hook_kernel, F, s, faces, F, (uint32_t)V, parent,
+                     r ? changed + r - 1 : (const int32_t*)nullptr, changed + r))
+      return rc;
+    if (int rc = run("cc_compress_kernel", cc_compress_kernel, V, s, V, parent, changed + r)) return rc;
   }
   return LIST_OK;
 }
@@ -405,27 +399,19 @@ int list_cc_finish(const int32_t* faces, int64_t V, int64_t F, void* workspace, 
     return fail(LIST_ERR_ARG, "component/roots/face_counts/vertex_counts/totals is NULL");
   if (int rc = check_workspace(V, F, workspace_bytes, &L)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (V == 0 || F == 0) {
-    hipLaunchKernelGGL(cc_empty_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, component, totals, V == 0 ? F : 0);
-    return launched("cc_empty_kernel");
-  }
-  char* ws = (char*)workspace;
-  const int32_t* parent = (const int32_t*)(ws + L.parent);
-  const uint8_t* used = (const uint8_t*)(ws + L.used);
-  int32_t* fcount = (int32_t*)(ws + L.fcount);
-  int32_t* vcount = (int32_t*)(ws + L.vcount);
-  int32_t* flag = (int32_t*)(ws + L.vflag);
-  int32_t* number = (int32_t*)(ws + L.vscan);
-  hipLaunchKernelGGL(cc_count_faces_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, faces, F, (uint32_t)V, parent, fcount);
-  if (int rc = launched("cc_count_faces_kernel")) return rc;
-  hipLaunchKernelGGL(cc_count_verts_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, parent, used, vcount);
-  if (int rc = launched("cc_count_verts_kernel")) return rc;
-  hipLaunchKernelGGL(cc_root_flag_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, parent, used, flag);
-  if (int rc = launched("cc_root_flag_kernel")) return rc;
-  if (int rc = scan(ws, L, flag, number, V, s)) return rc;
-  hipLaunchKernelGGL(cc_number_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, parent, used, flag, number, fcount,
-                     vcount, (const int32_t*)(ws + L.invalid), component, roots, face_counts, vertex_counts, totals);
-  return launched("cc_number_kernel");
+  if (V == 0 || F == 0) return run("cc_empty_kernel", cc_empty_kernel, V, s, V, component, totals, V == 0 ? F : 0);
+  const int32_t* parent = at<int32_t>(workspace, L.parent);
+  const uint8_t* used = at<uint8_t>(workspace, L.used);
+  int32_t* fcount = at<int32_t>(workspace, L.fcount);
+  int32_t* vcount = at<int32_t>(workspace, L.vcount);
+  int32_t* flag = at<int32_t>(workspace, L.vflag);
+  int32_t* number = at<int32_t>(workspace, L.vscan);
+  if (int rc = run("cc_count_faces_kernel", cc_count_faces_kernel, F, s, faces, F, (uint32_t)V, parent, fcount)) return rc;
+  if (int rc = run("cc_count_verts_kernel", cc_count_verts_kernel, V, s, V, parent, used, vcount)) return rc;
+  if (int rc = run("cc_root_flag_kernel", cc_root_flag_kernel, V, s, V, parent, used, flag)) return rc;
+  if (int rc = scan(workspace, L, flag, number, V, s)) return rc;
+  return run("cc_number_kernel", cc_number_kernel, V, s, V, parent, used, flag, number, fcount, vcount,
+             at<int32_t>(workspace, L.invalid), component, roots, face_counts, vertex_counts, totals);
 }
 
 int list_cc_compact(const float* verts, const int32_t* faces, int64_t V, int64_t F, const int32_t* component,
@@ -442,24 +428,19 @@ int list_cc_compact(const float* verts, const int32_t* faces, int64_t V, int64_t
   if (int rc = check_workspace(V, F, workspace_bytes, &L)) return rc;
   if (n_out_verts == 0) return LIST_OK;       // no kept vertex, so no kept face
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  int32_t* vflag = (int32_t*)(ws + L.vflag);
-  int32_t* vmap = (int32_t*)(ws + L.vscan);
-  int32_t* fflag = (int32_t*)(ws + L.fflag);
-  int32_t* fpos = (int32_t*)(ws + L.fscan);
-  hipLaunchKernelGGL(cc_keep_verts_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, V, component, keep, (uint32_t)K, vflag);
-  if (int rc = launched("cc_keep_verts_kernel")) return rc;
-  if (int rc = scan(ws, L, vflag, vmap, V, s)) return rc;
-  hipLaunchKernelGGL(cc_emit_verts_kernel, dim3(blocks(V)), dim3(kThreads), 0, s, (const uint32_t*)verts, V, vflag, vmap,
-                     (uint32_t*)out_verts, n_out_verts);
-  if (int rc = launched("cc_emit_verts_kernel")) return rc;
+  int32_t* vflag = at<int32_t>(workspace, L.vflag);
+  int32_t* vmap = at<int32_t>(workspace, L.vscan);
+  int32_t* fflag = at<int32_t>(workspace, L.fflag);
+  int32_t* fpos = at<int32_t>(workspace, L.fscan);
+  if (int rc = run("cc_keep_verts_kernel", cc_keep_verts_kernel, V, s, V, component, keep, (uint32_t)K, vflag)) return rc;
+  if (int rc = scan(workspace, L, vflag, vmap, V, s)) return rc;
+  if (int rc = run("cc_emit_verts_kernel", cc_emit_verts_kernel, V, s, (const uint32_t*)verts, V, vflag, vmap,
+                   (uint32_t*)out_verts, n_out_verts))
+    return rc;
   if (n_out_faces == 0) return LIST_OK;
-  hipLaunchKernelGGL(cc_keep_faces_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, faces, F, (uint32_t)V, vflag, fflag);
-  if (int rc = launched("cc_keep_faces_kernel")) return rc;
-  if (int rc = scan(ws, L, fflag, fpos, F, s)) return rc;
-  hipLaunchKernelGGL(cc_emit_faces_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, faces, F, fflag, fpos, vmap, out_faces,
-                     n_out_faces);
-  return launched("cc_emit_faces_kernel");
+  if (int rc = run("cc_keep_faces_kernel", cc_keep_faces_kernel, F, s, faces, F, (uint32_t)V, vflag, fflag)) return rc;
+  if (int rc = scan(workspace, L, fflag, fpos, F, s)) return rc;
+  return run("cc_emit_faces_kernel", cc_emit_faces_kernel, F, s, faces, F, fflag, fpos, vmap, out_faces, n_out_faces);
 }
 
 }  // extern "C"

@@ -316,11 +316,6 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restric
   }
 }
 
-template <int P>
-void launch_fps(const float* clouds, int64_t B, int32_t N, int32_t K, int32_t* idx, hipStream_t s) {
-  hipLaunchKernelGGL(fps_kernel<P>, dim3((unsigned)B), dim3(kFpsThreads), 0, s, clouds, N, K, idx);
-}
-
 }  // namespace
 
 extern "C" {
@@ -352,21 +347,18 @@ int list_data_signed_distance(const float* verts, int64_t n_verts, const int32_t
   if (n_points == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
   FacePrep* prep = (FacePrep*)workspace;
-  hipLaunchKernelGGL(face_prep_kernel, dim3((unsigned)((n_faces + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                     verts, n_verts, faces, n_faces, prep);
-  if (int rc = launched("face_prep_kernel")) return rc;
+  const dim3 block(kThreads);
+  if (int rc = launch("face_prep_kernel", face_prep_kernel, dim3(blocks_for(n_faces, kThreads)), block, s, verts,
+                      n_verts, faces, n_faces, prep))
+    return rc;
   // the most points per lane that still gives >= 1024 workgroups (4 per CU); fewer when Q is small
-  auto grid = [&](int R) { return (n_points + (int64_t)kThreads * R - 1) / ((int64_t)kThreads * R); };
-  if (grid(4) >= 1024)
-    hipLaunchKernelGGL(sdf_kernel<4>, dim3((unsigned)grid(4)), dim3(kThreads), 0, s, prep, n_faces, points, n_points,
-                       sdf, face_idx, winding);
-  else if (grid(2) >= 1024)
-    hipLaunchKernelGGL(sdf_kernel<2>, dim3((unsigned)grid(2)), dim3(kThreads), 0, s, prep, n_faces, points, n_points,
-                       sdf, face_idx, winding);
-  else
-    hipLaunchKernelGGL(sdf_kernel<1>, dim3((unsigned)grid(1)), dim3(kThreads), 0, s, prep, n_faces, points, n_points,
-                       sdf, face_idx, winding);
-  return launched("sdf_kernel");
+  auto grid = [&](int R) { return blocks_for(n_points, kThreads * R); };
+  auto run = [&](auto kernel, int R) {
+    return launch("sdf_kernel", kernel, dim3(grid(R)), block, s, prep, n_faces, points, n_points, sdf, face_idx, winding);
+  };
+  if (grid(4) >= 1024) return run(sdf_kernel<4>, 4);
+  if (grid(2) >= 1024) return run(sdf_kernel<2>, 2);
+  return run(sdf_kernel<1>, 1);
 }
 
 int list_data_boundary_samples(const float* points, int64_t n_points, float sigma, uint64_t seed, float* out,
@@ -375,9 +367,8 @@ int list_data_boundary_samples(const float* points, int64_t n_points, float sigm
     return fail(LIST_ERR_SHAPE, "%lld points: need 0 <= M <= INT32_MAX", (long long)n_points);
   if (n_points == 0) return LIST_OK;
   if (!points || !out) return fail(LIST_ERR_ARG, "points/out is NULL");
-  hipLaunchKernelGGL(boundary_kernel, dim3((unsigned)((n_points + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, points, n_points, (double)sigma, splitmix64(seed), out);
-  return launched("boundary_kernel");
+  return launch("boundary_kernel", boundary_kernel, dim3(blocks_for(n_points, kThreads)), dim3(kThreads),
+                (hipStream_t)stream, points, n_points, (double)sigma, splitmix64(seed), out);
 }
 
 int list_data_farthest_points(const float* clouds, int64_t n_clouds, int64_t n_points, int64_t k, int32_t* idx,
@@ -394,15 +385,17 @@ int list_data_farthest_points(const float* clouds, int64_t n_clouds, int64_t n_p
   if (!clouds || !idx) return fail(LIST_ERR_ARG, "clouds/idx is NULL");
   hipStream_t s = (hipStream_t)stream;
   const int32_t N = (int32_t)n_points, K = (int32_t)k;
-  const int64_t per_lane = (n_points + kFpsThreads - 1) / kFpsThreads;
-  if (per_lane <= 1) launch_fps<1>(clouds, n_clouds, N, K, idx, s);
-  else if (per_lane <= 2) launch_fps<2>(clouds, n_clouds, N, K, idx, s);
-  else if (per_lane <= 4) launch_fps<4>(clouds, n_clouds, N, K, idx, s);
-  else if (per_lane <= 8) launch_fps<8>(clouds, n_clouds, N, K, idx, s);
-  else if (per_lane <= 16) launch_fps<16>(clouds, n_clouds, N, K, idx, s);
-  else if (per_lane <= 32) launch_fps<32>(clouds, n_clouds, N, K, idx, s);
-  else launch_fps<64>(clouds, n_clouds, N, K, idx, s);
-  return launched("fps_kernel");
+  const int64_t per_lane = cdiv(n_points, kFpsThreads);
+  auto run = [&](auto kernel) {
+    return launch("fps_kernel", kernel, dim3((unsigned)n_clouds), dim3(kFpsThreads), s, clouds, N, K, idx);
+  };
+  if (per_lane <= 1) return run(fps_kernel<1>);
+  if (per_lane <= 2) return run(fps_kernel<2>);
+  if (per_lane <= 4) return run(fps_kernel<4>);
+  if (per_lane <= 8) return run(fps_kernel<8>);
+  if (per_lane <= 16) return run(fps_kernel<16>);
+  if (per_lane <= 32) return run(fps_kernel<32>);
+  return run(fps_kernel<64>);
 }
 
 }  // extern "C"

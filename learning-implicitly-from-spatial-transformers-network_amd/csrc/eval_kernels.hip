@@ -12,8 +12,8 @@
 #include <math.h>
 
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
+#include "list_cub.h"
 #include "list_eval.h"
 #include "list_host.h"
 
@@ -404,16 +404,14 @@ struct SampleLayout {
   size_t area, cdf, scratch, scratch_bytes, total;
 };
 
+// each layout: true, or false with the refusal's message set
 bool sample_layout(int64_t F, SampleLayout* L) {
-  size_t scratch = 0;
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, scratch, (const double*)nullptr, (double*)nullptr, (int)F) !=
-      hipSuccess)
-    return false;
-  L->area = 0;
-  L->cdf = align_up(F * sizeof(double));
-  L->scratch = L->cdf + align_up(F * sizeof(double));
-  L->scratch_bytes = scratch;
-  L->total = L->scratch + align_up(scratch);
+  if (!inclusive_sum_scratch<double>(F, &L->scratch_bytes)) return false;
+  Carver c;
+  L->area = c.take(F * sizeof(double));
+  L->cdf = c.take(F * sizeof(double));
+  L->scratch = c.take(L->scratch_bytes);
+  L->total = c.total();
   return true;
 }
 
@@ -428,33 +426,39 @@ bool contains_layout(int64_t F, int32_t res, ContainsLayout* L) {
   int bits = 1;
   while (((int64_t)1 << bits) <= (int64_t)res * res + 1) ++bits;
   L->key_bits = bits;
-  size_t scratch = 0;
-  if (hipcub::DeviceRadixSort::SortPairs(nullptr, scratch, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)F, 0, bits) != hipSuccess)
-    return false;
-  L->params = 0;
-  L->partial = align_up(sizeof(ContainsParams));
-  L->tri = L->partial + align_up(kRedBlocks * 6 * sizeof(double));
-  L->box = L->tri + align_up(F * 9 * sizeof(double));
-  L->keys_in = L->box + align_up(F * sizeof(uint64_t));
-  L->keys_out = L->keys_in + align_up(F * sizeof(uint32_t));
-  L->vals_in = L->keys_out + align_up(F * sizeof(uint32_t));
-  L->vals_out = L->vals_in + align_up(F * sizeof(uint32_t));
-  L->offsets = L->vals_out + align_up(F * sizeof(uint32_t));
-  L->scratch = L->offsets + align_up(L->n_off * sizeof(uint32_t));
-  L->scratch_bytes = scratch;
-  L->total = L->scratch + align_up(scratch);
+  if (!sort_pairs_scratch<uint32_t, uint32_t>(F, bits, &L->scratch_bytes)) return false;
+  Carver c;
+  L->params = c.take(sizeof(ContainsParams));
+  L->partial = c.take(kRedBlocks * 6 * sizeof(double));
+  L->tri = c.take(F * 9 * sizeof(double));
+  L->box = c.take(F * sizeof(uint64_t));
+  L->keys_in = c.take(F * sizeof(uint32_t));
+  L->keys_out = c.take(F * sizeof(uint32_t));
+  L->vals_in = c.take(F * sizeof(uint32_t));
+  L->vals_out = c.take(F * sizeof(uint32_t));
+  L->offsets = c.take(L->n_off * sizeof(uint32_t));
+  L->scratch = c.take(L->scratch_bytes);
+  L->total = c.total();
   return true;
 }
 
 // LIST_OK, or a refusal with its message
-int check_faces(int64_t V, int64_t F) {
+int check_n_faces(int64_t F) {
   if (F <= 0 || F > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld faces: need 1 <= F <= INT32_MAX", (long long)F);
-  if (V <= 0 || V > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld vertices: need 1 <= V <= INT32_MAX", (long long)V);
   return LIST_OK;
 }
 
-unsigned blocks(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+int check_hash_res(int32_t res) {
+  if (res < 1 || res > LIST_EVAL_MAX_HASH_RES)
+    return fail(LIST_ERR_SHAPE, "hash_res %d: need 1 <= res <= %d", res, LIST_EVAL_MAX_HASH_RES);
+  return LIST_OK;
+}
+
+int check_faces(int64_t V, int64_t F) {
+  if (int rc = check_n_faces(F)) return rc;
+  if (V <= 0 || V > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld vertices: need 1 <= V <= INT32_MAX", (long long)V);
+  return LIST_OK;
+}
 
 }  // namespace
 
@@ -472,27 +476,16 @@ int list_eval_nn(const float* src, int64_t n_src, const float* dst, int64_t n_ds
   if (!src || !dst || !dist || !idx) return fail(LIST_ERR_ARG, "src/dst/dist/idx is NULL");
   hipStream_t s = (hipStream_t)stream;
   // the most src points per lane that still gives >= 1024 workgroups (4 per CU); fewer when N is small
-  auto grid = [&](int R) { return (n_src + (int64_t)kNNThreads * R - 1) / ((int64_t)kNNThreads * R); };
-  if (grid(4) >= 1024)
-    hipLaunchKernelGGL(nn_kernel<4>, dim3((unsigned)grid(4)), dim3(kNNThreads), 0, s, src, n_src, dst, n_dst, dist, idx);
-  else if (grid(2) >= 1024)
-    hipLaunchKernelGGL(nn_kernel<2>, dim3((unsigned)grid(2)), dim3(kNNThreads), 0, s, src, n_src, dst, n_dst, dist, idx);
-  else
-    hipLaunchKernelGGL(nn_kernel<1>, dim3((unsigned)grid(1)), dim3(kNNThreads), 0, s, src, n_src, dst, n_dst, dist, idx);
-  return launched("nn_kernel");
+  auto grid = [&](int R) { return blocks_for(n_src, kNNThreads * R); };
+  const dim3 block(kNNThreads);
+  if (grid(4) >= 1024) return launch("nn_kernel", nn_kernel<4>, dim3(grid(4)), block, s, src, n_src, dst, n_dst, dist, idx);
+  if (grid(2) >= 1024) return launch("nn_kernel", nn_kernel<2>, dim3(grid(2)), block, s, src, n_src, dst, n_dst, dist, idx);
+  return launch("nn_kernel", nn_kernel<1>, dim3(grid(1)), block, s, src, n_src, dst, n_dst, dist, idx);
 }
 
 size_t list_eval_sample_workspace_bytes(int64_t n_faces) {
-  if (n_faces <= 0 || n_faces > INT32_MAX) {
-    fail(LIST_ERR_SHAPE, "%lld faces: need 1 <= F <= INT32_MAX", (long long)n_faces);
-    return 0;
-  }
   SampleLayout L;
-  if (!sample_layout(n_faces, &L)) {
-    fail(LIST_ERR_HIP, "hipcub::DeviceScan::InclusiveSum: scratch size query failed");
-    return 0;
-  }
-  return L.total;
+  return check_n_faces(n_faces) == LIST_OK && sample_layout(n_faces, &L) ? L.total : 0;
 }
 
 int list_eval_sample(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int64_t n_samples,
@@ -503,88 +496,70 @@ int list_eval_sample(const float* verts, int64_t n_verts, const int32_t* faces, 
   if (!verts || !faces || !workspace) return fail(LIST_ERR_ARG, "verts/faces/workspace is NULL");
   if (n_samples && (!points || !face_idx)) return fail(LIST_ERR_ARG, "points/face_idx is NULL");
   SampleLayout L;
-  if (!sample_layout(n_faces, &L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::InclusiveSum: scratch size query failed");
+  if (!sample_layout(n_faces, &L)) return LIST_ERR_HIP;
   if (workspace_bytes < L.total)
     return workspace_too_small(workspace_bytes, L.total, "list_eval_sample_workspace_bytes");
   if (n_samples == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  double* area = (double*)(ws + L.area);
-  double* cdf = (double*)(ws + L.cdf);
-  hipLaunchKernelGGL(face_area_kernel, dim3(blocks(n_faces)), dim3(kThreads), 0, s, verts, n_verts, faces, n_faces,
-                     area);
-  if (int rc = launched("face_area_kernel")) return rc;
-  size_t scratch = L.scratch_bytes;
-  hipError_t e = hipcub::DeviceScan::InclusiveSum(ws + L.scratch, scratch, area, cdf, (int)n_faces, s);
-  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceScan::InclusiveSum");
-  hipLaunchKernelGGL(sample_kernel, dim3(blocks(n_samples)), dim3(kThreads), 0, s, verts, n_verts, faces, n_faces, cdf,
-                     n_samples, splitmix64(seed), points, face_idx);
-  return launched("sample_kernel");
+  const dim3 block(kThreads);
+  double* area = at<double>(workspace, L.area);
+  double* cdf = at<double>(workspace, L.cdf);
+  if (int rc = launch("face_area_kernel", face_area_kernel, dim3(blocks_for(n_faces, kThreads)), block, s, verts,
+                      n_verts, faces, n_faces, area))
+    return rc;
+  if (int rc = inclusive_sum(at<char>(workspace, L.scratch), L.scratch_bytes, area, cdf, n_faces, s)) return rc;
+  return launch("sample_kernel", sample_kernel, dim3(blocks_for(n_samples, kThreads)), block, s, verts, n_verts, faces,
+                n_faces, cdf, n_samples, splitmix64(seed), points, face_idx);
 }
 
 size_t list_eval_contains_workspace_bytes(int64_t n_faces, int32_t hash_res) {
-  if (n_faces <= 0 || n_faces > INT32_MAX) {
-    fail(LIST_ERR_SHAPE, "%lld faces: need 1 <= F <= INT32_MAX", (long long)n_faces);
-    return 0;
-  }
-  if (hash_res < 1 || hash_res > LIST_EVAL_MAX_HASH_RES) {
-    fail(LIST_ERR_SHAPE, "hash_res %d: need 1 <= res <= %d", hash_res, LIST_EVAL_MAX_HASH_RES);
-    return 0;
-  }
+  if (check_n_faces(n_faces) != LIST_OK || check_hash_res(hash_res) != LIST_OK) return 0;
   ContainsLayout L;
-  if (!contains_layout(n_faces, hash_res, &L)) {
-    fail(LIST_ERR_HIP, "hipcub::DeviceRadixSort::SortPairs: scratch size query failed");
-    return 0;
-  }
-  return L.total;
+  return contains_layout(n_faces, hash_res, &L) ? L.total : 0;
 }
 
 int list_eval_contains(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
                        const double* points, int64_t n_points, const double* rot, int32_t hash_res, void* workspace,
                        size_t workspace_bytes, uint8_t* flags, void* stream) {
   if (int rc = check_faces(n_verts, n_faces)) return rc;
-  if (hash_res < 1 || hash_res > LIST_EVAL_MAX_HASH_RES)
-    return fail(LIST_ERR_SHAPE, "hash_res %d: need 1 <= res <= %d", hash_res, LIST_EVAL_MAX_HASH_RES);
+  if (int rc = check_hash_res(hash_res)) return rc;
   if (n_points < 0 || n_points > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld points", (long long)n_points);
   if (!verts || !faces || !workspace) return fail(LIST_ERR_ARG, "verts/faces/workspace is NULL");
   if (n_points && (!points || !flags)) return fail(LIST_ERR_ARG, "points/flags is NULL");
   ContainsLayout L;
-  if (!contains_layout(n_faces, hash_res, &L))
-    return fail(LIST_ERR_HIP, "hipcub::DeviceRadixSort::SortPairs: scratch size query failed");
+  if (!contains_layout(n_faces, hash_res, &L)) return LIST_ERR_HIP;
   if (workspace_bytes < L.total)
     return workspace_too_small(workspace_bytes, L.total, "list_eval_contains_workspace_bytes");
   if (n_points == 0) return LIST_OK;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  ContainsParams* P = (ContainsParams*)(ws + L.params);
-  double* partial = (double*)(ws + L.partial);
-  double* tri = (double*)(ws + L.tri);
-  uint64_t* box = (uint64_t*)(ws + L.box);
-  uint32_t* keys_in = (uint32_t*)(ws + L.keys_in);
-  uint32_t* keys_out = (uint32_t*)(ws + L.keys_out);
-  uint32_t* vals_in = (uint32_t*)(ws + L.vals_in);
-  uint32_t* vals_out = (uint32_t*)(ws + L.vals_out);
-  uint32_t* offsets = (uint32_t*)(ws + L.offsets);
+  ContainsParams* P = at<ContainsParams>(workspace, L.params);
+  double* partial = at<double>(workspace, L.partial);
+  double* tri = at<double>(workspace, L.tri);
+  uint64_t* box = at<uint64_t>(workspace, L.box);
+  uint32_t* keys_in = at<uint32_t>(workspace, L.keys_in);
+  uint32_t* keys_out = at<uint32_t>(workspace, L.keys_out);
+  uint32_t* vals_in = at<uint32_t>(workspace, L.vals_in);
+  uint32_t* vals_out = at<uint32_t>(workspace, L.vals_out);
+  uint32_t* offsets = at<uint32_t>(workspace, L.offsets);
   const int64_t F = n_faces;
-  hipLaunchKernelGGL(tri_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, verts, n_verts, faces, F, rot, tri);
-  if (int rc = launched("tri_kernel")) return rc;
-  const int nred = (int)(blocks(F) < (unsigned)kRedBlocks ? blocks(F) : (unsigned)kRedBlocks);
-  hipLaunchKernelGGL(bbox_partial_kernel, dim3(nred), dim3(kThreads), 0, s, faces, n_verts, F, tri, partial);
-  if (int rc = launched("bbox_partial_kernel")) return rc;
-  hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(kThreads), 0, s, partial, nred, (int)hash_res, P);
-  if (int rc = launched("bbox_final_kernel")) return rc;
-  hipLaunchKernelGGL(hash_key_kernel, dim3(blocks(F)), dim3(kThreads), 0, s, faces, n_verts, F, (int)hash_res, tri, P,
-                     box, keys_in, vals_in);
-  if (int rc = launched("hash_key_kernel")) return rc;
-  size_t scratch = L.scratch_bytes;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.scratch, scratch, keys_in, keys_out, vals_in, vals_out,
-                                                    (int)F, 0, L.key_bits, s);
-  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceRadixSort::SortPairs");
-  hipLaunchKernelGGL(cell_offsets_kernel, dim3(blocks(L.n_off)), dim3(kThreads), 0, s, keys_out, F, L.n_off, offsets);
-  if (int rc = launched("cell_offsets_kernel")) return rc;
-  hipLaunchKernelGGL(contains_kernel, dim3(blocks(n_points)), dim3(kThreads), 0, s, points, n_points, rot,
-                     (int)hash_res, P, tri, box, vals_out, offsets, flags);
-  return launched("contains_kernel");
+  const dim3 per_face(blocks_for(F, kThreads)), block(kThreads);
+  if (int rc = launch("tri_kernel", tri_kernel, per_face, block, s, verts, n_verts, faces, F, rot, tri)) return rc;
+  const int nred = (int)blocks_capped(F, kThreads, kRedBlocks);
+  if (int rc = launch("bbox_partial_kernel", bbox_partial_kernel, dim3(nred), block, s, faces, n_verts, F, tri, partial))
+    return rc;
+  if (int rc = launch("bbox_final_kernel", bbox_final_kernel, dim3(1), block, s, partial, nred, (int)hash_res, P))
+    return rc;
+  if (int rc = launch("hash_key_kernel", hash_key_kernel, per_face, block, s, faces, n_verts, F, (int)hash_res, tri, P,
+                      box, keys_in, vals_in))
+    return rc;
+  if (int rc = sort_pairs(at<char>(workspace, L.scratch), L.scratch_bytes, keys_in, keys_out, vals_in, vals_out, F,
+                          L.key_bits, s))
+    return rc;
+  if (int rc = launch("cell_offsets_kernel", cell_offsets_kernel, dim3(blocks_for(L.n_off, kThreads)), block, s,
+                      keys_out, F, L.n_off, offsets))
+    return rc;
+  return launch("contains_kernel", contains_kernel, dim3(blocks_for(n_points, kThreads)), block, s, points, n_points,
+                rot, (int)hash_res, P, tri, box, vals_out, offsets, flags);
 }
 
 }  // extern "C"

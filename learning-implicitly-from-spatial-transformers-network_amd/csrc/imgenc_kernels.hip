@@ -82,18 +82,17 @@ struct PackedLayout { ConvSlot conv[kConvs]; size_t head_w, head_b, total; };
 
 PackedLayout packed_layout(const Net& n) {
   PackedLayout p;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
+  Carver c;
   for (int k = 0; k < kSteps; ++k) {
     const Step& s = n.s[k];
     if (s.conv < 0) continue;
-    p.conv[s.conv].w = take(s.kind == STEM ? (size_t)kStemK * kStemC * 4 : wpk_bytes(s));
-    p.conv[s.conv].s = take((size_t)s.cout * 4);
-    p.conv[s.conv].t = take((size_t)s.cout * 4);
+    p.conv[s.conv].w = c.take(s.kind == STEM ? (size_t)kStemK * kStemC * 4 : wpk_bytes(s));
+    p.conv[s.conv].s = c.take((size_t)s.cout * 4);
+    p.conv[s.conv].t = c.take((size_t)s.cout * 4);
   }
-  p.head_w = take((size_t)kC4 * kVec * 4);
-  p.head_b = take((size_t)kVec * 4);
-  p.total = o;
+  p.head_w = c.take((size_t)kC4 * kVec * 4);
+  p.head_b = c.take((size_t)kVec * 4);
+  p.total = c.total();
   return p;
 }
 
@@ -102,14 +101,13 @@ struct WorkspaceLayout { size_t act[kSteps]; size_t total; };
 
 WorkspaceLayout workspace_layout(const Net& n, int B, int H, int W) {
   WorkspaceLayout w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
+  Carver c;
   for (int k = 0; k < kSteps; ++k) {
     const Step& s = n.s[k];
     w.act[k] = 0;
-    if (s.kind != HEAD) w.act[k] = take((size_t)B * (H >> s.shift_out) * (W >> s.shift_out) * s.cout * 2);
+    if (s.kind != HEAD) w.act[k] = c.take((size_t)B * (H >> s.shift_out) * (W >> s.shift_out) * s.cout * 2);
   }
-  w.total = o;
+  w.total = c.total();
   return w;
 }
 
@@ -336,22 +334,23 @@ __global__ __launch_bounds__(kThreads) void imgenc_conv_kernel(ConvArgs a) {
   }
 }
 
+// (a launch error of the forward is reported under the entry point's name, not the kernel's)
 template <int S, int KS>
-hipError_t launch_conv_nt(const ConvArgs& a, int B, int tiles, hipStream_t s) {
+int launch_conv_nt(const ConvArgs& a, int B, int tiles, hipStream_t s) {
   // 64 output channels per workgroup; narrower where that leaves the chip short of workgroups (the order of every
   // element's sum does not depend on the choice)
   const int64_t wg64 = (int64_t)tiles * B * (a.COUT / 64);
   const int nt = wg64 >= 512 ? 4 : wg64 >= 256 ? 2 : 1;
   const dim3 grid((unsigned)tiles, (unsigned)(a.COUT / (16 * nt)), (unsigned)B);
+  auto run = [&](auto kernel) { return launch("list_imgenc_forward", kernel, grid, dim3(kThreads), s, a); };
   switch (nt) {
-    case 4: hipLaunchKernelGGL((imgenc_conv_kernel<S, KS, 4>), grid, dim3(kThreads), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((imgenc_conv_kernel<S, KS, 2>), grid, dim3(kThreads), 0, s, a); break;
-    default: hipLaunchKernelGGL((imgenc_conv_kernel<S, KS, 1>), grid, dim3(kThreads), 0, s, a); break;
+    case 4: return run(imgenc_conv_kernel<S, KS, 4>);
+    case 2: return run(imgenc_conv_kernel<S, KS, 2>);
+    default: return run(imgenc_conv_kernel<S, KS, 1>);
   }
-  return hipGetLastError();
 }
 
-hipError_t launch_conv(ConvArgs a, int B, int ks, int stride, hipStream_t s) {
+int launch_conv(ConvArgs a, int B, int ks, int stride, hipStream_t s) {
   a.ntx = (a.Wo + kTx - 1) / kTx;
   const int tiles = a.ntx * ((a.Ho + kTy - 1) / kTy);
   if (ks == 1) return launch_conv_nt<2, 1>(a, B, tiles, s);
@@ -433,8 +432,6 @@ __global__ __launch_bounds__(kThreads) void imgenc_compose_kernel(const float* _
   }
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 int check_io(const ListImgencIO* io, const Net& net, const char* what) {
   if (!io) return fail(LIST_ERR_ARG, "%s: io is NULL", what);
   if (int rc = check_shape(io->B, io->H, io->W)) return rc;
@@ -490,27 +487,29 @@ int list_imgenc_prep_weights(const ListImgencParams* params, void* packed, size_
   if (!params->fc_w || !params->fc_b || !params->fc1_w || !params->fc1_b)
     return fail(LIST_ERR_ARG, "list_imgenc_prep_weights: fc_w, fc_b, fc1_w or fc1_b is NULL");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)packed;
+  const char* const name = "list_imgenc_prep_weights";      // a launch error is reported under the entry point's name
+  const dim3 block(kThreads);
   for (int k = 0; k < kSteps; ++k) {
     const Step& st = net.s[k];
     if (st.conv < 0) continue;
     const ListImgencConv& cv = params->conv[st.conv];
     const ConvSlot& slot = P.conv[st.conv];
+    int rc;
     if (st.kind == STEM) {
-      hipLaunchKernelGGL(imgenc_stem_pack_kernel, dim3(blocks_for(kStemK * kStemC)), dim3(kThreads), 0, s, cv.w,
-                         (float*)(base + slot.w));
+      rc = launch(name, imgenc_stem_pack_kernel, dim3(blocks_for(kStemK * kStemC, kThreads)), block, s, cv.w,
+                  at<float>(packed, slot.w));
     } else {
       const int total = (int)(wpk_bytes(st) / 2);
-      hipLaunchKernelGGL(imgenc_pack_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, cv.w, st.cin, st.cout, st.ks,
-                         (_Float16*)(base + slot.w), total);
+      rc = launch(name, imgenc_pack_kernel, dim3(blocks_for(total, kThreads)), block, s, cv.w, st.cin, st.cout, st.ks,
+                  at<_Float16>(packed, slot.w), total);
     }
-    list::launch_bn_fold(cv.bn_weight, cv.bn_bias, cv.bn_mean, cv.bn_var, cv.bn_eps, st.cout, (float*)(base + slot.s),
-                         (float*)(base + slot.t), s);
-    if (int rc = launched("list_imgenc_prep_weights")) return rc;
+    if (rc) return rc;
+    list::launch_bn_fold(cv.bn_weight, cv.bn_bias, cv.bn_mean, cv.bn_var, cv.bn_eps, st.cout, at<float>(packed, slot.s),
+                         at<float>(packed, slot.t), s);
+    if ((rc = launched(name))) return rc;
   }
-  hipLaunchKernelGGL(imgenc_compose_kernel, dim3(blocks_for((kC4 + 1) * kVec)), dim3(kThreads), 0, s, params->fc_w,
-                     params->fc_b, params->fc1_w, params->fc1_b, (float*)(base + P.head_w), (float*)(base + P.head_b));
-  return launched("list_imgenc_prep_weights");
+  return launch(name, imgenc_compose_kernel, dim3(blocks_for((kC4 + 1) * kVec, kThreads)), block, s, params->fc_w,
+                params->fc_b, params->fc1_w, params->fc1_b, at<float>(packed, P.head_w), at<float>(packed, P.head_b));
 }
 
 int list_imgenc_forward_steps(const ListImgencIO* io, int32_t step_begin, int32_t step_end, void* stream) {
@@ -521,26 +520,24 @@ int list_imgenc_forward_steps(const ListImgencIO* io, int32_t step_begin, int32_
   const int B = io->B, H = io->H, W = io->W;
   const WorkspaceLayout WS = workspace_layout(net, B, H, W);
   hipStream_t s = (hipStream_t)stream;
-  const char* pk = (const char*)io->packed;
-  char* ws = (char*)io->workspace;
-  auto f = [&](size_t off) { return (const float*)(pk + off); };
-  auto act = [&](int k) { return (_Float16*)(ws + WS.act[k]); };
+  const void* pk = io->packed;
+  auto f = [&](size_t off) { return at<float>(pk, off); };
+  auto act = [&](int k) { return at<_Float16>(io->workspace, WS.act[k]); };
+  const char* const name = "list_imgenc_forward";      // a launch error is reported under the entry point's name
 
   for (int k = step_begin; k < step_end; ++k) {
     const Step& st = net.s[k];
     const int Ho = H >> st.shift_out, Wo = W >> st.shift_out;
-    hipError_t e = hipSuccess;
+    int rc;
     if (st.kind == STEM) {
       const ConvSlot& c = P.conv[0];
       const dim3 grid((unsigned)((H / kStemTile) * (W / kStemTile)), (unsigned)B);
-      hipLaunchKernelGGL(imgenc_stem_kernel, grid, dim3(kThreads), 0, s, io->img, io->img_sb, io->img_sc, io->img_sh,
-                         io->img_sw, H, W, f(c.w), f(c.s), f(c.t), io->levels_out[0], act(k));
-      e = hipGetLastError();
+      rc = launch(name, imgenc_stem_kernel, grid, dim3(kThreads), s, io->img, io->img_sb, io->img_sc, io->img_sh,
+                  io->img_sw, H, W, f(c.w), f(c.s), f(c.t), io->levels_out[0], act(k));
     } else if (st.kind == POOL) {
       const int64_t total = (int64_t)B * Ho * Wo * 8;
-      hipLaunchKernelGGL(imgenc_pool_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, act(st.in), act(k), H, W,
-                         total);
-      e = hipGetLastError();
+      rc = launch(name, imgenc_pool_kernel, dim3(blocks_for(total, kThreads)), dim3(kThreads), s, act(st.in), act(k), H,
+                  W, total);
     } else if (st.kind == CONV) {
       const ConvSlot& c = P.conv[st.conv];
       ConvArgs a;
@@ -548,19 +545,18 @@ int list_imgenc_forward_steps(const ListImgencIO* io, int32_t step_begin, int32_
       a.idt = st.idt >= 0 ? act(st.idt) : nullptr;
       a.out = act(k);
       a.level = st.level >= 0 ? io->levels_out[st.level] : nullptr;
-      a.w = (const list::f16x8*)(pk + c.w);
+      a.w = at<list::f16x8>(pk, c.w);
       a.s = f(c.s);
       a.t = f(c.t);
       a.Ho = Ho; a.Wo = Wo;
       a.Hi = Ho * st.stride; a.Wi = Wo * st.stride;
       a.CIN = st.cin; a.COUT = st.cout; a.relu = st.relu;
-      e = launch_conv(a, B, st.ks, st.stride, s);
+      rc = launch_conv(a, B, st.ks, st.stride, s);
     } else {
-      hipLaunchKernelGGL(imgenc_head_kernel, dim3((unsigned)B), dim3(kHeadThreads), 0, s,
-                         (const float*)io->levels_out[kLevels - 1], Ho * Wo, f(P.head_w), f(P.head_b), io->vec);
-      e = hipGetLastError();
+      rc = launch(name, imgenc_head_kernel, dim3((unsigned)B), dim3(kHeadThreads), s,
+                  (const float*)io->levels_out[kLevels - 1], Ho * Wo, f(P.head_w), f(P.head_b), io->vec);
     }
-    if (e != hipSuccess) return hip_fail(e, "list_imgenc_forward");
+    if (rc) return rc;
   }
   return LIST_OK;
 }

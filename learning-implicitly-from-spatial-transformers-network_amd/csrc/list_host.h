@@ -55,3 +55,31 @@ static bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace regions start on 256 bytes
 
 static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Workgroups of `threads` that cover n items, and the same clamped to [1, cap] (for kernels that stride over the grid)
+static unsigned blocks_for(int64_t n, int threads) { return (unsigned)cdiv(n, threads); }
+static unsigned blocks_capped(int64_t n, int threads, int64_t cap) {
+  const int64_t b = cdiv(n, threads);
+  return (unsigned)(b < 1 ? 1 : b < cap ? b : cap);
+}
+
+// Carves "region a | region b | ... " out of a workspace or a packed blob: take(bytes) is where the region starts, and
+// the next one starts align_up(bytes) later.  Every region so starts on 256 bytes, which is why advancing by
+// `o += align_up(bytes)` and by `o = align_up(o + bytes)` give the same offsets: for o a multiple of 256 the two are equal.
+struct Carver {
+  size_t next = 0;
+  size_t take(size_t bytes) { const size_t at = next; next += align_up(bytes); return at; }
+  size_t total() const { return next; }
+};
+
+// The region at byte offset `off` of a workspace, as T
+template <typename T> static T* at(void* ws, size_t off) { return (T*)((char*)ws + off); }
+template <typename T> static const T* at(const void* ws, size_t off) { return (const T*)((const char*)ws + off); }
+
+// Launches `kernel` (no dynamic LDS: no stage uses any) and returns launched(name):
+//   if (int rc = launch("mc_count_kernel", mc_count_kernel, grid, block, s, volume, X, ...)) return rc;
+template <typename K, typename... Args>
+static int launch(const char* name, K kernel, dim3 grid, dim3 block, hipStream_t stream, Args... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
+  return launched(name);
+}

@@ -382,20 +382,28 @@ int check_shape(int64_t B, int64_t N, int64_t M) {
   return LIST_OK;
 }
 
+// ---- workspace: packed u64 [B (N + M)] | partial f64 [2 B] | per side (targets T, sources S: N, M then M, N):
+//                 cnt i32 [B T] | end i32 [B T] | ord i32 [B S] ----
 Layout layout(int64_t B, int64_t N, int64_t M) {
   Layout L;
-  L.packed = 0;
-  L.partial = L.packed + align_up((size_t)(B * (N + M)) * sizeof(unsigned long long));
-  size_t o = L.partial + align_up((size_t)(2 * B) * sizeof(double));
+  Carver c;
+  L.packed = c.take((size_t)(B * (N + M)) * sizeof(unsigned long long));
+  L.partial = c.take((size_t)(2 * B) * sizeof(double));
   const int64_t T[2] = {N, M}, S[2] = {M, N};
   for (int s = 0; s < 2; ++s) {
-    L.cnt[s] = o;
-    L.end[s] = L.cnt[s] + align_up((size_t)(B * T[s]) * sizeof(int32_t));
-    L.ord[s] = L.end[s] + align_up((size_t)(B * T[s]) * sizeof(int32_t));
-    o = L.ord[s] + align_up((size_t)(B * S[s]) * sizeof(int32_t));
+    L.cnt[s] = c.take((size_t)(B * T[s]) * sizeof(int32_t));
+    L.end[s] = c.take((size_t)(B * T[s]) * sizeof(int32_t));
+    L.ord[s] = c.take((size_t)(B * S[s]) * sizeof(int32_t));
   }
-  L.total = o;
+  L.total = c.total();
   return L;
+}
+
+// the workspace of both entry points: its layout, then its size
+int check_ws(int64_t B, int64_t N, int64_t M, size_t workspace_bytes, Layout* L) {
+  *L = layout(B, N, M);
+  if (workspace_bytes < L->total) return workspace_too_small(workspace_bytes, L->total, "list_chamfer_workspace_bytes");
+  return LIST_OK;
 }
 
 }  // namespace
@@ -405,8 +413,7 @@ extern "C" {
 const char* list_loss_last_error(void) { return g_err; }
 
 size_t list_chamfer_workspace_bytes(int64_t B, int64_t N, int64_t M) {
-  if (check_shape(B, N, M) != LIST_OK) return 0;
-  return layout(B, N, M).total;
+  return check_shape(B, N, M) == LIST_OK ? layout(B, N, M).total : 0;
 }
 
 int list_chamfer_fwd(const float* x, const float* y, int64_t B, int64_t N, int64_t M, float* d2_xy, int32_t* idx_xy,
@@ -415,23 +422,21 @@ int list_chamfer_fwd(const float* x, const float* y, int64_t B, int64_t N, int64
   if (int rc = check_shape(B, N, M)) return rc;
   if (!x || !y || !d2_xy || !idx_xy || !d2_yx || !idx_yx || !loss || !workspace)
     return fail(LIST_ERR_ARG, "x/y/d2_xy/idx_xy/d2_yx/idx_yx/loss/workspace is NULL");
-  const Layout L = layout(B, N, M);
-  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_chamfer_workspace_bytes");
+  Layout L;
+  if (int rc = check_ws(B, N, M, workspace_bytes, &L)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  unsigned long long* packed = (unsigned long long*)(ws + L.packed);
-  double* partial = (double*)(ws + L.partial);
+  unsigned long long* packed = at<unsigned long long>(workspace, L.packed);
+  double* partial = at<double>(workspace, L.partial);
   hipError_t e = hipMemsetAsync(packed, 0xFF, (size_t)(B * (N + M)) * sizeof(unsigned long long), s);
   if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
   const FwdGrid g = fwd_grid(B, N, M);
-  hipLaunchKernelGGL(nn_sq_kernel, dim3((unsigned)(B * (g.sx * g.tx + g.sy * g.ty))), dim3(kFwdThreads), 0, s, x, y,
-                     g, packed);
-  if (int rc = launched("nn_sq_kernel")) return rc;
-  hipLaunchKernelGGL(loss_partial_kernel, dim3((unsigned)(2 * B)), dim3(kRedThreads), 0, s, x, y, B, N, M, packed,
-                     d2_xy, idx_xy, d2_yx, idx_yx, partial);
-  if (int rc = launched("loss_partial_kernel")) return rc;
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1), 0, s, partial, B, N, M, loss);
-  return launched("loss_final_kernel");
+  if (int rc = launch("nn_sq_kernel", nn_sq_kernel, dim3((unsigned)(B * (g.sx * g.tx + g.sy * g.ty))),
+                      dim3(kFwdThreads), s, x, y, g, packed))
+    return rc;
+  if (int rc = launch("loss_partial_kernel", loss_partial_kernel, dim3((unsigned)(2 * B)), dim3(kRedThreads), s, x, y,
+                      B, N, M, packed, d2_xy, idx_xy, d2_yx, idx_yx, partial))
+    return rc;
+  return launch("loss_final_kernel", loss_final_kernel, dim3(1), dim3(1), s, partial, B, N, M, loss);
 }
 
 int list_chamfer_bwd(const float* x, const float* y, int64_t B, int64_t N, int64_t M, const int32_t* idx_xy,
@@ -441,14 +446,14 @@ int list_chamfer_bwd(const float* x, const float* y, int64_t B, int64_t N, int64
   if (!x || !y || !idx_xy || !idx_yx || !grad_loss || !workspace)
     return fail(LIST_ERR_ARG, "x/y/idx_xy/idx_yx/grad_loss/workspace is NULL");
   if (!grad_x && !grad_y) return fail(LIST_ERR_ARG, "grad_x and grad_y are both NULL");
-  const Layout L = layout(B, N, M);
-  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_chamfer_workspace_bytes");
+  Layout L;
+  if (int rc = check_ws(B, N, M, workspace_bytes, &L)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
   const bool want[2] = {grad_x != nullptr, grad_y != nullptr};
+  auto i32 = [&](size_t off) { return at<int32_t>(workspace, off); };
   CsrSide side[2];
-  side[0] = CsrSide{idx_yx, (int32_t*)(ws + L.cnt[0]), (int32_t*)(ws + L.end[0]), (int32_t*)(ws + L.ord[0]), M, N};
-  side[1] = CsrSide{idx_xy, (int32_t*)(ws + L.cnt[1]), (int32_t*)(ws + L.end[1]), (int32_t*)(ws + L.ord[1]), N, M};
+  side[0] = CsrSide{idx_yx, i32(L.cnt[0]), i32(L.end[0]), i32(L.ord[0]), M, N};
+  side[1] = CsrSide{idx_xy, i32(L.cnt[1]), i32(L.end[1]), i32(L.ord[1]), N, M};
   CsrArgs a{};
   a.B = B;
   for (int k = 0; k < 2; ++k) {
@@ -459,16 +464,15 @@ int list_chamfer_bwd(const float* x, const float* y, int64_t B, int64_t N, int64
     a.hist_blocks[a.nsides] = cdiv(B * side[k].S, kHistThreads);
     ++a.nsides;
   }
-  hipLaunchKernelGGL(csr_hist_kernel, dim3((unsigned)(a.hist_blocks[0] + a.hist_blocks[1])), dim3(kHistThreads), 0, s,
-                     a);
-  if (int rc = launched("csr_hist_kernel")) return rc;
-  hipLaunchKernelGGL(csr_place_kernel, dim3((unsigned)(a.nsides * B)), dim3(kPlaceThreads), 0, s, a);
-  if (int rc = launched("csr_place_kernel")) return rc;
+  if (int rc = launch("csr_hist_kernel", csr_hist_kernel, dim3((unsigned)(a.hist_blocks[0] + a.hist_blocks[1])),
+                      dim3(kHistThreads), s, a))
+    return rc;
+  if (int rc = launch("csr_place_kernel", csr_place_kernel, dim3((unsigned)(a.nsides * B)), dim3(kPlaceThreads), s, a))
+    return rc;
   GradArgs ga{x, y, B, N, M, idx_xy, idx_yx, grad_loss, grad_x, grad_y, {side[0], side[1]},
               want[0] ? cdiv(B * N, kGradThreads) : 0};
   const int64_t blocks_y = want[1] ? cdiv(B * M, kGradThreads) : 0;
-  hipLaunchKernelGGL(grad_kernel, dim3((unsigned)(ga.blocks_x + blocks_y)), dim3(kGradThreads), 0, s, ga);
-  return launched("grad_kernel");
+  return launch("grad_kernel", grad_kernel, dim3((unsigned)(ga.blocks_x + blocks_y)), dim3(kGradThreads), s, ga);
 }
 
 }  // extern "C"

@@ -8,8 +8,8 @@
 //   mc_emit_kernel    per point with something to write: its vertices, and its cell's triangles, whose vertex numbers
 //                     come from the scan and the masks of the points owning the cell's edges.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
+#include "list_cub.h"
 #include "list_host.h"
 #include "list_mesh.h"
 #include "mc_tables.h"
@@ -163,19 +163,24 @@ int check_shape(int32_t X, int32_t Y, int32_t Z) {
   return LIST_OK;
 }
 
+// the layout, or false with the refusal's message set
 bool layout(int32_t X, int32_t Y, int32_t Z, Layout* L) {
   const size_t N = (size_t)X * Y * Z;
-  size_t scratch = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scratch, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N) !=
-      hipSuccess)
-    return false;
-  L->counts = 0;
-  L->offsets = align_up(N * sizeof(uint64_t));
-  L->info = L->offsets + align_up(N * sizeof(uint64_t));
-  L->scratch = L->info + align_up(N * sizeof(uint16_t));
-  L->scratch_bytes = scratch;
-  L->total = L->scratch + align_up(scratch);
+  if (!exclusive_sum_scratch<uint64_t>((int64_t)N, &L->scratch_bytes)) return false;
+  Carver c;
+  L->counts = c.take(N * sizeof(uint64_t));
+  L->offsets = c.take(N * sizeof(uint64_t));
+  L->info = c.take(N * sizeof(uint16_t));
+  L->scratch = c.take(L->scratch_bytes);
+  L->total = c.total();
   return true;
+}
+
+// the workspace of the entry points that take one: its layout, then its size
+int check_ws(int32_t X, int32_t Y, int32_t Z, size_t workspace_bytes, Layout* L) {
+  if (!layout(X, Y, Z, L)) return LIST_ERR_HIP;
+  if (workspace_bytes < L->total) return workspace_too_small(workspace_bytes, L->total, "list_mc_workspace_bytes");
+  return LIST_OK;
 }
 
 }  // namespace
@@ -185,13 +190,8 @@ extern "C" {
 const char* list_mesh_last_error(void) { return g_err; }
 
 size_t list_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (check_shape(X, Y, Z) != LIST_OK) return 0;
   Layout L;
-  if (!layout(X, Y, Z, &L)) {
-    fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-    return 0;
-  }
-  return L.total;
+  return check_shape(X, Y, Z) == LIST_OK && layout(X, Y, Z, &L) ? L.total : 0;
 }
 
 int list_mc_count(const float* volume, int32_t X, int32_t Y, int32_t Z, float level, void* workspace,
@@ -199,22 +199,17 @@ int list_mc_count(const float* volume, int32_t X, int32_t Y, int32_t Z, float le
   if (int rc = check_shape(X, Y, Z)) return rc;
   if (!volume || !workspace || !totals) return fail(LIST_ERR_ARG, "volume/workspace/totals is NULL");
   Layout L;
-  if (!layout(X, Y, Z, &L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_mc_workspace_bytes");
+  if (int rc = check_ws(X, Y, Z, workspace_bytes, &L)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint64_t* counts = (uint64_t*)(ws + L.counts);
-  uint64_t* offsets = (uint64_t*)(ws + L.offsets);
-  uint16_t* info = (uint16_t*)(ws + L.info);
+  uint64_t* counts = at<uint64_t>(workspace, L.counts);
+  uint64_t* offsets = at<uint64_t>(workspace, L.offsets);
   const dim3 grid((Z + kTK - 1) / kTK, (Y + kTJ - 1) / kTJ, (X + kTI - 1) / kTI);
-  hipLaunchKernelGGL(mc_count_kernel, grid, dim3(kTK, kTJ), 0, s, volume, X, Y, Z, level, counts, info);
-  if (int rc = launched("mc_count_kernel")) return rc;
+  if (int rc = launch("mc_count_kernel", mc_count_kernel, grid, dim3(kTK, kTJ), s, volume, X, Y, Z, level, counts,
+                      at<uint16_t>(workspace, L.info)))
+    return rc;
   const int64_t N = (int64_t)X * Y * Z;
-  size_t scratch = L.scratch_bytes;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, counts, offsets, (int)N, s);
-  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceScan::ExclusiveSum");
-  hipLaunchKernelGGL(mc_totals_kernel, dim3(1), dim3(1), 0, s, counts, offsets, N - 1, totals);
-  return launched("mc_totals_kernel");
+  if (int rc = exclusive_sum(at<char>(workspace, L.scratch), L.scratch_bytes, counts, offsets, N, s)) return rc;
+  return launch("mc_totals_kernel", mc_totals_kernel, dim3(1), dim3(1), s, counts, offsets, N - 1, totals);
 }
 
 int list_mc_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float level, const float bb_min[3],
@@ -228,20 +223,16 @@ int list_mc_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float lev
   if (n_verts > INT32_MAX) return fail(LIST_ERR_SHAPE, "%lld vertices exceed INT32_MAX", (long long)n_verts);
   if ((n_verts && !verts) || (n_faces && !faces)) return fail(LIST_ERR_ARG, "verts/faces is NULL");
   Layout L;
-  if (!layout(X, Y, Z, &L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-  if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_mc_workspace_bytes");
+  if (int rc = check_ws(X, Y, Z, workspace_bytes, &L)) return rc;
   if (n_verts == 0 && n_faces == 0) return LIST_OK;
-  hipStream_t s = (hipStream_t)stream;
   const int dims[3] = {X, Y, Z};
   float scale[3];
   for (int a = 0; a < 3; ++a) scale[a] = (float)(((double)bb_max[a] - (double)bb_min[a]) / (dims[a] - 1));
-  const char* ws = (const char*)workspace;
   const int64_t N = (int64_t)X * Y * Z;
-  hipLaunchKernelGGL(mc_emit_kernel, dim3((unsigned)((N + kEmitThreads - 1) / kEmitThreads)), dim3(kEmitThreads), 0,
-                     s, volume, X, Y, Z, level, bb_min[0], bb_min[1], bb_min[2], scale[0], scale[1], scale[2],
-                     (const uint64_t*)(ws + L.offsets), (const uint16_t*)(ws + L.info), verts, n_verts, faces,
-                     n_faces);
-  return launched("mc_emit_kernel");
+  return launch("mc_emit_kernel", mc_emit_kernel, dim3(blocks_for(N, kEmitThreads)), dim3(kEmitThreads),
+                (hipStream_t)stream, volume, X, Y, Z, level, bb_min[0], bb_min[1], bb_min[2], scale[0], scale[1],
+                scale[2], at<uint64_t>(workspace, L.offsets), at<uint16_t>(workspace, L.info), verts, n_verts, faces,
+                n_faces);
 }
 
 }  // extern "C"

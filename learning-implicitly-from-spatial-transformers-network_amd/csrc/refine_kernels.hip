@@ -11,8 +11,8 @@
 //   refine_fill_kernel      one thread per fine point: lattice value, refined value or trilinear interpolation.
 // No atomics: every output element has exactly one writer, so the results are deterministic.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
+#include "list_cub.h"
 #include "list_host.h"
 #include "list_refine.h"
 
@@ -190,20 +190,23 @@ int check_shape(int32_t R, int32_t s) {
   return LIST_OK;
 }
 
-bool layout(int32_t R, int32_t s, Layout* L) {
+// the regions before the scan scratch: host arithmetic only
+void carve(int32_t R, int32_t s, Carver* c, Layout* L) {
   const Dims d = dims_of(R, s);
   const size_t nb3 = (size_t)d.NB * d.NB * d.NB, N = (size_t)R * R * R;
-  size_t scratch = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scratch, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N) !=
-      hipSuccess)
-    return false;
-  L->active = 0;
-  L->dilated = align_up(nb3);
-  L->flags = L->dilated + align_up(nb3);
-  L->offsets = L->flags + align_up(N * sizeof(uint32_t));
-  L->scratch = L->offsets + align_up(N * sizeof(uint32_t));
-  L->scratch_bytes = scratch;
-  L->total = L->scratch + align_up(scratch);
+  L->active = c->take(nb3);
+  L->dilated = c->take(nb3);
+  L->flags = c->take(N * sizeof(uint32_t));
+  L->offsets = c->take(N * sizeof(uint32_t));
+}
+
+// the layout, or false with the refusal's message set
+bool layout(int32_t R, int32_t s, Layout* L) {
+  if (!exclusive_sum_scratch<uint32_t>((int64_t)R * R * R, &L->scratch_bytes)) return false;
+  Carver c;
+  carve(R, s, &c, L);
+  L->scratch = c.take(L->scratch_bytes);
+  L->total = c.total();
   return true;
 }
 
@@ -211,12 +214,10 @@ bool layout(int32_t R, int32_t s, Layout* L) {
 int check_ws(int32_t R, int32_t s, const void* workspace, size_t workspace_bytes, Layout* L) {
   if (int rc = check_shape(R, s)) return rc;
   if (!workspace) return fail(LIST_ERR_ARG, "workspace is NULL");
-  if (!layout(R, s, L)) return fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
+  if (!layout(R, s, L)) return LIST_ERR_HIP;
   if (workspace_bytes < L->total) return workspace_too_small(workspace_bytes, L->total, "list_refine_workspace_bytes");
   return LIST_OK;
 }
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
 
@@ -225,19 +226,16 @@ extern "C" {
 const char* list_refine_last_error(void) { return g_err; }
 
 size_t list_refine_workspace_bytes(int32_t R, int32_t s) {
-  if (check_shape(R, s) != LIST_OK) return 0;
   Layout L;
-  if (!layout(R, s, &L)) {
-    fail(LIST_ERR_HIP, "hipcub::DeviceScan::ExclusiveSum: scratch size query failed");
-    return 0;
-  }
-  return L.total;
+  return check_shape(R, s) == LIST_OK && layout(R, s, &L) ? L.total : 0;
 }
 
 size_t list_refine_mask_offset(int32_t R, int32_t s) {
   if (check_shape(R, s) != LIST_OK) return 0;
-  const Dims d = dims_of(R, s);
-  return align_up((size_t)d.NB * d.NB * d.NB);
+  Carver c;
+  Layout L;
+  carve(R, s, &c, &L);
+  return L.dilated;
 }
 
 int list_refine_count(const float* lattice, int32_t R, int32_t s, float level, float band, void* workspace,
@@ -250,24 +248,18 @@ int list_refine_count(const float* lattice, int32_t R, int32_t s, float level, f
   if (int rc = check_ws(R, s, workspace, workspace_bytes, &L)) return rc;
   const Dims d = dims_of(R, s);
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint8_t* active = (uint8_t*)(ws + L.active);
-  uint8_t* dilated = (uint8_t*)(ws + L.dilated);
-  uint32_t* flags = (uint32_t*)(ws + L.flags);
-  uint32_t* offsets = (uint32_t*)(ws + L.offsets);
+  uint8_t* active = at<uint8_t>(workspace, L.active);
+  uint8_t* dilated = at<uint8_t>(workspace, L.dilated);
+  uint32_t* flags = at<uint32_t>(workspace, L.flags);
+  uint32_t* offsets = at<uint32_t>(workspace, L.offsets);
   const int64_t nb3 = (int64_t)d.NB * d.NB * d.NB, N = (int64_t)R * R * R;
-  hipLaunchKernelGGL(refine_classify_kernel, dim3(blocks_for(nb3)), dim3(kThreads), 0, st, lattice, d, level, band,
-                     active);
-  if (int rc = launched("refine_classify_kernel")) return rc;
-  hipLaunchKernelGGL(refine_dilate_kernel, dim3(blocks_for(nb3)), dim3(kThreads), 0, st, active, d, dilated);
-  if (int rc = launched("refine_dilate_kernel")) return rc;
-  hipLaunchKernelGGL(refine_flag_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, st, dilated, d, flags);
-  if (int rc = launched("refine_flag_kernel")) return rc;
-  size_t scratch = L.scratch_bytes;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(ws + L.scratch, scratch, flags, offsets, (int)N, st);
-  if (e != hipSuccess) return hip_fail(e, "hipcub::DeviceScan::ExclusiveSum");
-  hipLaunchKernelGGL(refine_total_kernel, dim3(1), dim3(1), 0, st, flags, offsets, N - 1, total);
-  return launched("refine_total_kernel");
+  const dim3 bricks(blocks_for(nb3, kThreads)), points(blocks_for(N, kThreads)), block(kThreads);
+  if (int rc = launch("refine_classify_kernel", refine_classify_kernel, bricks, block, st, lattice, d, level, band, active))
+    return rc;
+  if (int rc = launch("refine_dilate_kernel", refine_dilate_kernel, bricks, block, st, active, d, dilated)) return rc;
+  if (int rc = launch("refine_flag_kernel", refine_flag_kernel, points, block, st, dilated, d, flags)) return rc;
+  if (int rc = exclusive_sum(at<char>(workspace, L.scratch), L.scratch_bytes, flags, offsets, N, st)) return rc;
+  return launch("refine_total_kernel", refine_total_kernel, dim3(1), dim3(1), st, flags, offsets, N - 1, total);
 }
 
 int list_refine_emit(int32_t R, int32_t s, double lo, double hi, const void* workspace, size_t workspace_bytes,
@@ -280,13 +272,11 @@ int list_refine_emit(int32_t R, int32_t s, double lo, double hi, const void* wor
   Layout L;
   if (int rc = check_ws(R, s, workspace, workspace_bytes, &L)) return rc;
   if (n == 0) return LIST_OK;
-  const char* ws = (const char*)workspace;
   const int64_t N = (int64_t)R * R * R;
   const double step = (hi - lo) / (R - 1);
-  hipLaunchKernelGGL(refine_emit_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, (hipStream_t)stream,
-                     (const uint32_t*)(ws + L.flags), (const uint32_t*)(ws + L.offsets), R, lo, hi, step, coords,
-                     indices, n);
-  return launched("refine_emit_kernel");
+  return launch("refine_emit_kernel", refine_emit_kernel, dim3(blocks_for(N, kThreads)), dim3(kThreads),
+                (hipStream_t)stream, at<uint32_t>(workspace, L.flags), at<uint32_t>(workspace, L.offsets), R, lo, hi,
+                step, coords, indices, n);
 }
 
 int list_refine_fill(const float* lattice, const float* values, int64_t n, int32_t R, int32_t s,
@@ -297,12 +287,10 @@ int list_refine_fill(const float* lattice, const float* values, int64_t n, int32
   if (n && !values) return fail(LIST_ERR_ARG, "values is NULL");
   Layout L;
   if (int rc = check_ws(R, s, workspace, workspace_bytes, &L)) return rc;
-  const char* ws = (const char*)workspace;
   const int64_t N = (int64_t)R * R * R;
-  hipLaunchKernelGGL(refine_fill_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, (hipStream_t)stream, lattice,
-                     values, n, (const uint32_t*)(ws + L.flags), (const uint32_t*)(ws + L.offsets), dims_of(R, s),
-                     volume);
-  return launched("refine_fill_kernel");
+  return launch("refine_fill_kernel", refine_fill_kernel, dim3(blocks_for(N, kThreads)), dim3(kThreads),
+                (hipStream_t)stream, lattice, values, n, at<uint32_t>(workspace, L.flags),
+                at<uint32_t>(workspace, L.offsets), dims_of(R, s), volume);
 }
 
 }  // extern "C"

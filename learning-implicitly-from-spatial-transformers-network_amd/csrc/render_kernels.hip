@@ -182,10 +182,11 @@ int check_sizes(int64_t V, int64_t F, int64_t H, int64_t W) {
 
 Layout layout(int64_t F, int64_t H, int64_t W) {
   Layout L;
-  L.keys = 0;
-  L.list = L.keys + align_up((size_t)(H * W) * sizeof(Key));
-  L.counters = L.list + align_up((size_t)(F > 0 ? F : 1) * sizeof(int32_t));
-  L.total = L.counters + align_up((1 + RENDER_N_STATS) * sizeof(int32_t));
+  Carver c;
+  L.keys = c.take((size_t)(H * W) * sizeof(Key));
+  L.list = c.take((size_t)(F > 0 ? F : 1) * sizeof(int32_t));
+  L.counters = c.take((1 + RENDER_N_STATS) * sizeof(int32_t));
+  L.total = c.total();
   return L;
 }
 
@@ -197,8 +198,6 @@ int check_camera(const ListRenderCamera* cam) {
     return fail(LIST_ERR_ARG, "camera map_size %d: the LIST camera needs a plane of at least 2 x 2", cam->map_size);
   return LIST_OK;
 }
-
-unsigned blocks(int64_t n) { return (unsigned)(n < 1 ? 1 : (cdiv(n, kThreads) < kMaxBlocks ? cdiv(n, kThreads) : kMaxBlocks)); }
 
 }  // namespace
 
@@ -224,29 +223,26 @@ int list_render_rasterize(const float* verts, int64_t V, const int32_t* faces, i
   const Layout L = layout(F, H, W);
   if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_render_workspace_bytes");
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  Key* keys = (Key*)(ws + L.keys);
-  int32_t* list = (int32_t*)(ws + L.list);
-  int32_t* count = (int32_t*)(ws + L.counters);
+  Key* keys = at<Key>(workspace, L.keys);
+  int32_t* list = at<int32_t>(workspace, L.list);
+  int32_t* count = at<int32_t>(workspace, L.counters);
   int32_t* ws_stats = count + 1;
   const int64_t n_pixels = H * W;
+  const dim3 per_pixel(blocks_capped(n_pixels, kThreads, kMaxBlocks)), block(kThreads);
   for (int step = step_begin; step < step_end; ++step) {
-    if (step == 0) {
-      hipLaunchKernelGGL(k_render_clear, dim3(blocks(n_pixels)), dim3(kThreads), 0, s, keys, n_pixels, count, ws_stats);
-      if (int rc = launched("k_render_clear")) return rc;
-    } else if (step == 1 && F > 0) {
-      hipLaunchKernelGGL(k_render_setup_small, dim3((unsigned)cdiv(F, kThreads)), dim3(kThreads), 0, s, verts, (uint32_t)V,
-                         faces, F, *camera, (int)W, (int)H, z_near, keys, list, count, ws_stats);
-      if (int rc = launched("k_render_setup_small")) return rc;
-    } else if (step == 2 && F > 0) {
-      hipLaunchKernelGGL(k_render_large, dim3(LIST_RENDER_LARGE_GROUPS), dim3(kThreads), 0, s, verts, (uint32_t)V, faces, F,
-                         *camera, (int)W, (int)H, z_near, keys, (const int32_t*)list, (const int32_t*)count);
-      if (int rc = launched("k_render_large")) return rc;
-    } else if (step == 3) {
-      hipLaunchKernelGGL(k_render_resolve, dim3(blocks(n_pixels)), dim3(kThreads), 0, s, (const Key*)keys, n_pixels,
-                         camera->mode, (const int32_t*)ws_stats, face_id, depth, stats);
-      if (int rc = launched("k_render_resolve")) return rc;
-    }
+    int rc = LIST_OK;
+    if (step == 0)
+      rc = launch("k_render_clear", k_render_clear, per_pixel, block, s, keys, n_pixels, count, ws_stats);
+    else if (step == 1 && F > 0)
+      rc = launch("k_render_setup_small", k_render_setup_small, dim3(blocks_for(F, kThreads)), block, s, verts,
+                  (uint32_t)V, faces, F, *camera, (int)W, (int)H, z_near, keys, list, count, ws_stats);
+    else if (step == 2 && F > 0)
+      rc = launch("k_render_large", k_render_large, dim3(LIST_RENDER_LARGE_GROUPS), block, s, verts, (uint32_t)V, faces,
+                  F, *camera, (int)W, (int)H, z_near, keys, list, count);
+    else if (step == 3)
+      rc = launch("k_render_resolve", k_render_resolve, per_pixel, block, s, keys, n_pixels, camera->mode, ws_stats,
+                  face_id, depth, stats);
+    if (rc) return rc;
   }
   return LIST_OK;
 }
@@ -261,9 +257,9 @@ int list_render_shade(const float* verts, int64_t V, const int32_t* faces, int64
   if ((V && !verts) || (F && !faces)) return fail(LIST_ERR_ARG, "verts/faces is NULL");
   if (!face_id || !rgb) return fail(LIST_ERR_ARG, "face_id/rgb is NULL");
   const int64_t n_pixels = H * W;
-  hipLaunchKernelGGL(k_render_shade, dim3(blocks(n_pixels)), dim3(kThreads), 0, (hipStream_t)stream, verts, (uint32_t)V,
-                     faces, (uint32_t)F, face_id, *camera, n_pixels, (int)shade, background, (int)alpha256, rgb);
-  return launched("k_render_shade");
+  return launch("k_render_shade", k_render_shade, dim3(blocks_capped(n_pixels, kThreads, kMaxBlocks)), dim3(kThreads),
+                (hipStream_t)stream, verts, (uint32_t)V, faces, (uint32_t)F, face_id, *camera, n_pixels, (int)shade,
+                background, (int)alpha256, rgb);
 }
 
 }  // extern "C"

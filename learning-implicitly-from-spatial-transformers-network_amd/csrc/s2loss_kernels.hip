@@ -297,12 +297,14 @@ struct Layout {
   size_t occ, sdf, same, total;
 };
 
+// ---- workspace: occ partials f64 [2 kOccGroups] | sdf partials f64 [2 kSdfGroups] | same u64 [kSdfGroups] ----
 Layout layout() {
   Layout L;
-  L.occ = 0;
-  L.sdf = L.occ + align_up((size_t)2 * kOccGroups * sizeof(double));
-  L.same = L.sdf + align_up((size_t)2 * kSdfGroups * sizeof(double));
-  L.total = L.same + align_up((size_t)kSdfGroups * sizeof(unsigned long long));
+  Carver c;
+  L.occ = c.take((size_t)2 * kOccGroups * sizeof(double));
+  L.sdf = c.take((size_t)2 * kSdfGroups * sizeof(double));
+  L.same = c.take((size_t)kSdfGroups * sizeof(unsigned long long));
+  L.total = c.total();
   return L;
 }
 
@@ -317,10 +319,7 @@ int check_shape(int64_t n_occ, int64_t B, int64_t N, int kind) {
   return LIST_OK;
 }
 
-int grad_groups(const Cut& c) {
-  const int64_t g = cdiv(c.items, (int64_t)kThreads * kUnroll);
-  return (int)(g < 1 ? 1 : g > kGradGroupsMax ? kGradGroupsMax : g);
-}
+unsigned grad_groups(const Cut& c) { return blocks_capped(c.items, kThreads * kUnroll, kGradGroupsMax); }
 
 }  // namespace
 
@@ -343,34 +342,32 @@ int list_s2loss_fwd(const float* occ, const void* occ_gt, int occ_gt_kind, int64
   const Layout L = layout();
   if (workspace_bytes < L.total) return workspace_too_small(workspace_bytes, L.total, "list_s2loss_workspace_bytes");
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  double* occ_partial = (double*)(ws + L.occ);
-  double* sdf_partial = (double*)(ws + L.sdf);
-  unsigned long long* same = (unsigned long long*)(ws + L.same);
+  double* occ_partial = at<double>(workspace, L.occ);
+  double* sdf_partial = at<double>(workspace, L.sdf);
+  unsigned long long* same = at<unsigned long long>(workspace, L.same);
   const dim3 block(kThreads);
   const Cut co = cut(occ, occ_gt, occ_gt_kind ? 1 : 4, nullptr, n_occ);
+  auto occ_sum = [&](auto kernel, auto gt) {
+    return launch("occ_sum_kernel", kernel, dim3(kOccGroups), block, s, occ, gt, co, n_occ, occ_partial);
+  };
+  int rc;
   if (occ_gt_kind == 0) {
     const float* gt = (const float*)occ_gt;
-    if (co.width == 4) hipLaunchKernelGGL((occ_sum_kernel<float, 4>), dim3(kOccGroups), block, 0, s, occ, gt, co, n_occ, occ_partial);
-    else hipLaunchKernelGGL((occ_sum_kernel<float, 1>), dim3(kOccGroups), block, 0, s, occ, gt, co, n_occ, occ_partial);
+    rc = co.width == 4 ? occ_sum(occ_sum_kernel<float, 4>, gt) : occ_sum(occ_sum_kernel<float, 1>, gt);
   } else {
     const uint8_t* gt = (const uint8_t*)occ_gt;
-    if (co.width == 4) hipLaunchKernelGGL((occ_sum_kernel<uint8_t, 4>), dim3(kOccGroups), block, 0, s, occ, gt, co, n_occ, occ_partial);
-    else hipLaunchKernelGGL((occ_sum_kernel<uint8_t, 1>), dim3(kOccGroups), block, 0, s, occ, gt, co, n_occ, occ_partial);
+    rc = co.width == 4 ? occ_sum(occ_sum_kernel<uint8_t, 4>, gt) : occ_sum(occ_sum_kernel<uint8_t, 1>, gt);
   }
-  if (int rc = launched("occ_sum_kernel")) return rc;
+  if (rc) return rc;
   const int64_t BN = B * N;
   const Cut cs = cut(sdf_pred, sdf_gt, 4, nullptr, BN);
-  if (cs.width == 4)
-    hipLaunchKernelGGL((sdf_sum_kernel<4>), dim3(kSdfGroups), block, 0, s, sdf_pred, sdf_gt, cs, BN, (double)sdf_scale,
-                       sdf_partial, same);
-  else
-    hipLaunchKernelGGL((sdf_sum_kernel<1>), dim3(kSdfGroups), block, 0, s, sdf_pred, sdf_gt, cs, BN, (double)sdf_scale,
-                       sdf_partial, same);
-  if (int rc = launched("sdf_sum_kernel")) return rc;
-  hipLaunchKernelGGL(final_kernel, dim3(1), block, 0, s, occ_partial, sdf_partial, same, (double)n_occ, (double)B,
-                     (double)BN, (double)w, out);
-  return launched("final_kernel");
+  auto sdf_sum = [&](auto kernel) {
+    return launch("sdf_sum_kernel", kernel, dim3(kSdfGroups), block, s, sdf_pred, sdf_gt, cs, BN, (double)sdf_scale,
+                  sdf_partial, same);
+  };
+  if ((rc = cs.width == 4 ? sdf_sum(sdf_sum_kernel<4>) : sdf_sum(sdf_sum_kernel<1>))) return rc;
+  return launch("final_kernel", final_kernel, dim3(1), block, s, occ_partial, sdf_partial, same, (double)n_occ,
+                (double)B, (double)BN, (double)w, out);
 }
 
 int list_s2loss_bwd(const float* occ, const void* occ_gt, int occ_gt_kind, int64_t n_occ, const float* sdf_pred,
@@ -387,29 +384,29 @@ int list_s2loss_bwd(const float* occ, const void* occ_gt, int occ_gt_kind, int64
     const Cut c = cut(occ, occ_gt, occ_gt_kind ? 1 : 4, grad_occ, n_occ);
     const dim3 grid(grad_groups(c));
     const double k = 1000.0 / (double)n_occ, wd = (double)w;
+    auto occ_grad = [&](auto kernel, auto gt) {
+      return launch("occ_grad_kernel", kernel, grid, block, s, occ, gt, c, n_occ, grad_out, k, wd, grad_occ);
+    };
+    int rc;
     if (occ_gt_kind == 0) {
       const float* gt = (const float*)occ_gt;
-      if (c.width == 4) hipLaunchKernelGGL((occ_grad_kernel<float, 4>), grid, block, 0, s, occ, gt, c, n_occ, grad_out, k, wd, grad_occ);
-      else hipLaunchKernelGGL((occ_grad_kernel<float, 1>), grid, block, 0, s, occ, gt, c, n_occ, grad_out, k, wd, grad_occ);
+      rc = c.width == 4 ? occ_grad(occ_grad_kernel<float, 4>, gt) : occ_grad(occ_grad_kernel<float, 1>, gt);
     } else {
       const uint8_t* gt = (const uint8_t*)occ_gt;
-      if (c.width == 4) hipLaunchKernelGGL((occ_grad_kernel<uint8_t, 4>), grid, block, 0, s, occ, gt, c, n_occ, grad_out, k, wd, grad_occ);
-      else hipLaunchKernelGGL((occ_grad_kernel<uint8_t, 1>), grid, block, 0, s, occ, gt, c, n_occ, grad_out, k, wd, grad_occ);
+      rc = c.width == 4 ? occ_grad(occ_grad_kernel<uint8_t, 4>, gt) : occ_grad(occ_grad_kernel<uint8_t, 1>, gt);
     }
-    if (int rc = launched("occ_grad_kernel")) return rc;
+    if (rc) return rc;
   }
   if (grad_sdf_pred) {
     const int64_t BN = B * N;
     const Cut c = cut(sdf_pred, sdf_gt, 4, grad_sdf_pred, BN);
     const dim3 grid(grad_groups(c));
     const double k = -2.0 / (double)B;
-    if (c.width == 4)
-      hipLaunchKernelGGL((sdf_grad_kernel<4>), grid, block, 0, s, sdf_pred, sdf_gt, c, BN, grad_out, k, (double)sdf_scale,
-                         grad_sdf_pred);
-    else
-      hipLaunchKernelGGL((sdf_grad_kernel<1>), grid, block, 0, s, sdf_pred, sdf_gt, c, BN, grad_out, k, (double)sdf_scale,
-                         grad_sdf_pred);
-    if (int rc = launched("sdf_grad_kernel")) return rc;
+    auto sdf_grad = [&](auto kernel) {
+      return launch("sdf_grad_kernel", kernel, grid, block, s, sdf_pred, sdf_gt, c, BN, grad_out, k, (double)sdf_scale,
+                    grad_sdf_pred);
+    };
+    return c.width == 4 ? sdf_grad(sdf_grad_kernel<4>) : sdf_grad(sdf_grad_kernel<1>);
   }
   return LIST_OK;
 }
@@ -417,10 +414,8 @@ int list_s2loss_bwd(const float* occ, const void* occ_gt, int occ_gt_kind, int64
 int list_s2loss_log(const float* x, int64_t n, double* out, void* stream) {
   if (n < 1 || n > kMaxElems) return fail(LIST_ERR_SHAPE, "n = %lld: need 1 <= n <= 2^36", (long long)n);
   if (!x || !out) return fail(LIST_ERR_ARG, "%s is NULL", !x ? "x" : "out");
-  const int64_t g = cdiv(n, kThreads);
-  hipLaunchKernelGGL(log_kernel, dim3((unsigned)(g > kGradGroupsMax ? kGradGroupsMax : g)), dim3(kThreads), 0,
-                     (hipStream_t)stream, x, n, out);
-  return launched("log_kernel");
+  return launch("log_kernel", log_kernel, dim3(blocks_capped(n, kThreads, kGradGroupsMax)), dim3(kThreads),
+                (hipStream_t)stream, x, n, out);
 }
 
 }  // extern "C"

@@ -47,23 +47,22 @@ struct PackedLayout {
 
 PackedLayout packed_layout(const int32_t* layers) {
   PackedLayout p;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
+  Carver c;
   for (int l = 0; l < kStages; ++l) {
     const int cin = layers[l], cout = layers[l + 1];
-    p.conv[l].w = take(cin == 1 ? (size_t)cout * kTaps * 4 : wpk_bytes(cin, cout));
-    p.conv[l].bias = take((size_t)cout * 4);
+    p.conv[l].w = c.take(cin == 1 ? (size_t)cout * kTaps * 4 : wpk_bytes(cin, cout));
+    p.conv[l].bias = c.take((size_t)cout * 4);
     p.conv[l].s = p.conv[l].t = 0;
     p.conv2[l] = ConvSlot{0, 0, 0, 0};
-    if (l < 2) { p.conv[l].s = take((size_t)cout * 4); p.conv[l].t = take((size_t)cout * 4); }
+    if (l < 2) { p.conv[l].s = c.take((size_t)cout * 4); p.conv[l].t = c.take((size_t)cout * 4); }
     if (l >= 3) {
-      p.conv2[l].w = take(wpk_bytes(cout, cout));
-      p.conv2[l].bias = take((size_t)cout * 4);
-      p.conv2[l].s = take((size_t)cout * 4);
-      p.conv2[l].t = take((size_t)cout * 4);
+      p.conv2[l].w = c.take(wpk_bytes(cout, cout));
+      p.conv2[l].bias = c.take((size_t)cout * 4);
+      p.conv2[l].s = c.take((size_t)cout * 4);
+      p.conv2[l].t = c.take((size_t)cout * 4);
     }
   }
-  p.total = o;
+  p.total = c.total();
   return p;
 }
 
@@ -71,24 +70,23 @@ struct WorkspaceLayout { size_t t0, t1, mid, pooled[kStages], total; };
 
 WorkspaceLayout workspace_layout(int B, int R, const int32_t* layers) {
   WorkspaceLayout w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
+  Carver c;
   const size_t r3 = (size_t)R * R * R;
-  w.t0 = take((size_t)B * r3 * 4);
-  w.t1 = take((size_t)B * r3 * 4);
+  w.t0 = c.take((size_t)B * r3 * 4);
+  w.t1 = c.take((size_t)B * r3 * 4);
   size_t mid = 0;
   for (int l = 3; l < kStages; ++l) {
     const size_t D = (size_t)(R >> (l - 3));
     const size_t b = (size_t)B * D * D * D * layers[l + 1] * 2;
     if (b > mid) mid = b;
   }
-  w.mid = take(mid);
+  w.mid = c.take(mid);
   for (int l = 0; l < kStages; ++l) w.pooled[l] = 0;
   for (int l = 3; l < kStages - 1; ++l) {
     const size_t D = (size_t)(R >> (l - 2));
-    w.pooled[l] = take((size_t)B * D * D * D * layers[l + 1] * 2);
+    w.pooled[l] = c.take((size_t)B * D * D * D * layers[l + 1] * 2);
   }
-  w.total = o;
+  w.total = c.total();
   return w;
 }
 
@@ -359,18 +357,19 @@ __global__ __launch_bounds__(kThreads) void voxenc_conv_kernel(ConvArgs a) {
   }
 }
 
+// (a launch error of the forward is reported under the entry point's name, not the kernel's)
 template <int CC>
-hipError_t launch_conv_nt(const ConvArgs& a, int cout, dim3 grid, hipStream_t s) {
+int launch_conv_nt(const ConvArgs& a, int cout, dim3 grid, hipStream_t s) {
+  auto run = [&](auto kernel) { return launch("list_voxenc_forward", kernel, grid, dim3(kThreads), s, a); };
   switch (cout) {
-    case 16: hipLaunchKernelGGL((voxenc_conv_kernel<CC, 1>), grid, dim3(kThreads), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((voxenc_conv_kernel<CC, 2>), grid, dim3(kThreads), 0, s, a); break;
-    case 64: hipLaunchKernelGGL((voxenc_conv_kernel<CC, 4>), grid, dim3(kThreads), 0, s, a); break;
-    default: hipLaunchKernelGGL((voxenc_conv_kernel<CC, 8>), grid, dim3(kThreads), 0, s, a); break;
+    case 16: return run(voxenc_conv_kernel<CC, 1>);
+    case 32: return run(voxenc_conv_kernel<CC, 2>);
+    case 64: return run(voxenc_conv_kernel<CC, 4>);
+    default: return run(voxenc_conv_kernel<CC, 8>);
   }
-  return hipGetLastError();
 }
 
-hipError_t launch_conv(ConvArgs a, int B, int cout, hipStream_t s) {
+int launch_conv(ConvArgs a, int B, int cout, hipStream_t s) {
   a.nbx = (a.D + kBx - 1) / kBx;
   a.nby = (a.D + kBy - 1) / kBy;
   const int nbz = (a.D + kBz - 1) / kBz;
@@ -398,8 +397,6 @@ __global__ __launch_bounds__(kThreads) void voxenc_copy_kernel(const float* __re
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i < n) out[i] = in[i];
 }
-
-unsigned blocks_for(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
 
@@ -437,33 +434,32 @@ int list_voxenc_prep_weights(const ListVoxencStage* stages, const int32_t* layer
       return fail(LIST_ERR_ARG, "list_voxenc_prep_weights: stage %d: a BN array is NULL", l);
   }
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)packed;
+  const char* const name = "list_voxenc_prep_weights";      // a launch error is reported under the entry point's name
+  auto copy = [&](const float* src, size_t off, int n) {
+    return launch(name, voxenc_copy_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), s, src,
+                  at<float>(packed, off), n);
+  };
+  auto pack = [&](const float* src, int cin, int cout, size_t off) {
+    const int total = (int)(wpk_bytes(cin, cout) / 2);
+    return launch(name, voxenc_pack_kernel, dim3(blocks_for(total, kThreads)), dim3(kThreads), s, src, cin, cout,
+                  at<_Float16>(packed, off), total);
+  };
   for (int l = 0; l < kStages; ++l) {
     const ListVoxencStage& st = stages[l];
     const int cin = layers[l], cout = layers[l + 1];
-    if (cin == 1) {
-      hipLaunchKernelGGL(voxenc_copy_kernel, dim3(blocks_for(cout * kTaps)), dim3(kThreads), 0, s, st.conv_w,
-                         (float*)(base + P.conv[l].w), cout * kTaps);
-    } else {
-      const int total = (int)(wpk_bytes(cin, cout) / 2);
-      hipLaunchKernelGGL(voxenc_pack_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, st.conv_w, cin, cout,
-                         (_Float16*)(base + P.conv[l].w), total);
-    }
-    hipLaunchKernelGGL(voxenc_copy_kernel, dim3(blocks_for(cout)), dim3(kThreads), 0, s, st.conv_b,
-                       (float*)(base + P.conv[l].bias), cout);
+    if (int rc = cin == 1 ? copy(st.conv_w, P.conv[l].w, cout * kTaps) : pack(st.conv_w, cin, cout, P.conv[l].w))
+      return rc;
+    if (int rc = copy(st.conv_b, P.conv[l].bias, cout)) return rc;
     const ConvSlot* bn_slot = l < 2 ? &P.conv[l] : nullptr;
     if (l >= 3) {
-      const int total = (int)(wpk_bytes(cout, cout) / 2);
-      hipLaunchKernelGGL(voxenc_pack_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, st.conv2_w, cout, cout,
-                         (_Float16*)(base + P.conv2[l].w), total);
-      hipLaunchKernelGGL(voxenc_copy_kernel, dim3(blocks_for(cout)), dim3(kThreads), 0, s, st.conv2_b,
-                         (float*)(base + P.conv2[l].bias), cout);
+      if (int rc = pack(st.conv2_w, cout, cout, P.conv2[l].w)) return rc;
+      if (int rc = copy(st.conv2_b, P.conv2[l].bias, cout)) return rc;
       bn_slot = &P.conv2[l];
     }
-    if (bn_slot)
-      list::launch_bn_fold(st.bn_weight, st.bn_bias, st.bn_mean, st.bn_var, st.bn_eps, cout, (float*)(base + bn_slot->s),
-                           (float*)(base + bn_slot->t), s);
-    if (int rc = launched("list_voxenc_prep_weights")) return rc;
+    if (!bn_slot) continue;
+    list::launch_bn_fold(st.bn_weight, st.bn_bias, st.bn_mean, st.bn_var, st.bn_eps, cout, at<float>(packed, bn_slot->s),
+                         at<float>(packed, bn_slot->t), s);
+    if (int rc = launched(name)) return rc;
   }
   return LIST_OK;
 }
@@ -485,57 +481,54 @@ int list_voxenc_forward_steps(const float* occ, int32_t B, int32_t R, const int3
   if (int rc = check_step_range("list_voxenc_forward_steps", step_begin, step_end, 3 + 2 * (kStages - 3))) return rc;
 
   hipStream_t s = (hipStream_t)stream;
-  const char* pk = (const char*)packed;
-  char* ws = (char*)workspace;
-  float* t0 = (float*)(ws + W.t0);
-  float* t1 = (float*)(ws + W.t1);
-  _Float16* mid = (_Float16*)(ws + W.mid);
-  auto f = [&](size_t off) { return (const float*)(pk + off); };
+  float* t0 = at<float>(workspace, W.t0);
+  float* t1 = at<float>(workspace, W.t1);
+  _Float16* mid = at<_Float16>(workspace, W.mid);
+  auto f = [&](size_t off) { return at<float>(packed, off); };
   const dim3 tiles((unsigned)((R / kTile) * (R / kTile) * (R / kTile)), (unsigned)B);
+  const char* const name = "list_voxenc_forward";      // a launch error is reported under the entry point's name
 
   for (int step = step_begin; step < step_end; ++step) {
-    hipError_t e = hipSuccess;
+    int rc;
     if (step < 3) {                                     // stages 0 .. 2, one channel
       const float* in = step == 0 ? occ : step == 1 ? t0 : t1;
       float* out = step == 0 ? t0 : step == 1 ? t1 : (float*)levels_out[0];
       const ConvSlot& c = P.conv[step];
-      hipLaunchKernelGGL(voxenc_stencil_kernel, tiles, dim3(kThreads), 0, s, in, out, (int)R, f(c.w), f(c.bias),
-                         step < 2 ? f(c.s) : nullptr, step < 2 ? f(c.t) : nullptr, step < 2 ? 0 : 1);
-      e = hipGetLastError();
+      rc = launch(name, voxenc_stencil_kernel, tiles, dim3(kThreads), s, in, out, (int)R, f(c.w), f(c.bias),
+                  step < 2 ? f(c.s) : nullptr, step < 2 ? f(c.t) : nullptr, step < 2 ? 0 : 1);
     } else {
       const int l = 3 + (step - 3) / 2;
       const bool second = (step - 3) % 2 == 1;
       const int D = R >> (l - 3);
       const int cin = layers[l], cout = layers[l + 1];
       if (!second && l == 3) {
-        hipLaunchKernelGGL(voxenc_expand_kernel, tiles, dim3(kThreads), 0, s, (const float*)levels_out[0], mid, (int)R,
-                           cout, f(P.conv[3].w), f(P.conv[3].bias));
-        e = hipGetLastError();
+        rc = launch(name, voxenc_expand_kernel, tiles, dim3(kThreads), s, (const float*)levels_out[0], mid, (int)R, cout,
+                    f(P.conv[3].w), f(P.conv[3].bias));
       } else {
         ConvArgs a;
         a.D = D;
         if (!second) {
-          a.in = (const _Float16*)(ws + W.pooled[l - 1]);
+          a.in = at<_Float16>(workspace, W.pooled[l - 1]);
           a.out = mid;
           a.pooled = nullptr;
-          a.w = (const list::f16x8*)(pk + P.conv[l].w);
+          a.w = at<list::f16x8>(packed, P.conv[l].w);
           a.bias = f(P.conv[l].bias);
           a.s = a.t = nullptr;
           a.CIN = cin;
         } else {
           a.in = mid;
           a.out = (_Float16*)levels_out[l - 2];
-          a.pooled = l < kStages - 1 ? (_Float16*)(ws + W.pooled[l]) : nullptr;
-          a.w = (const list::f16x8*)(pk + P.conv2[l].w);
+          a.pooled = l < kStages - 1 ? at<_Float16>(workspace, W.pooled[l]) : nullptr;
+          a.w = at<list::f16x8>(packed, P.conv2[l].w);
           a.bias = f(P.conv2[l].bias);
           a.s = f(P.conv2[l].s);
           a.t = f(P.conv2[l].t);
           a.CIN = cout;
         }
-        e = launch_conv(a, B, cout, s);
+        rc = launch_conv(a, B, cout, s);
       }
     }
-    if (e != hipSuccess) return hip_fail(e, "list_voxenc_forward");
+    if (rc) return rc;
   }
   return LIST_OK;
 }
