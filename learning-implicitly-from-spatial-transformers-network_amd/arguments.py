@@ -34,6 +34,10 @@ def build_parser():
                         "(components.py, on the device, before export and --eval_pred); 0 keeps all")
     p.add_argument("--mesh_min_faces", type=int, default=0,
                    help="drop the connected components of the predicted mesh with fewer faces than this; 0 drops none")
+    p.add_argument("--mesh_simplify", type=int, default=0,
+                   help="simplify the predicted mesh by vertex clustering on a C x C x C grid over [--bb_min, --bb_max] "
+                        "(simplify.py, on the device, after the component filter and before export, rendering and "
+                        "--eval_pred); 1 ... 1024, 0 = off")
     p.add_argument("--render_pred", default="none", choices=["none", "view", "canonical", "both"],
                    help="pictures of the predicted mesh beside its _pred.obj (render.py, on the device): 'view' from the "
                         "model's own camera (the predicted or given trans_mat) over the input image (_pred_view.png), "

@@ -190,8 +190,8 @@ def marching_cubes_cpu(volume, level=0.0, bb_min=-0.5, bb_max=0.5):
 
 # ---- mesh -----------------------------------------------------------------------------------------------------------
 class Mesh:
-    """vertices float32 [V,3] and faces int32 [F,3] (0-based) on the host.  Made from CUDA tensors (as marching_cubes
-    and components.keep_components return them) it also keeps those, for render()."""
+    """vertices float32 [V,3] and faces int32 [F,3] (0-based) on the host.  Made from CUDA tensors (as marching_cubes,
+    components.keep_components and simplify.simplify return them) it also keeps those, for render()."""
 
     def __init__(self, vertices, faces):
         self._device = None
@@ -235,6 +235,14 @@ class Mesh:
         with return_info also its info dict."""
         from . import components
         v, f, info = components.keep_components_cpu(self.vertices, self.faces, keep, min_faces)
+        m = Mesh(v, f)
+        return (m, info) if return_info else m
+
+    def simplify(self, cells, bb_min=-0.5, bb_max=0.5, return_info=False):
+        """A new Mesh with the vertices of every cell of the `cells` grid over [bb_min, bb_max] merged into one
+        (simplify.py's rule), on the host (simplify.simplify_cpu); with return_info also its info dict."""
+        from . import simplify as S
+        v, f, info = S.simplify_cpu(self.vertices, self.faces, cells, bb_min, bb_max)
         m = Mesh(v, f)
         return (m, info) if return_info else m
 

@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, render, s2loss, utils
+from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, render, s2loss, simplify, utils
 from . import losses as L
 
 
@@ -105,6 +105,11 @@ class LIST:
             raise ValueError(f"mesh_components and mesh_min_faces must be >= 0 (got {self.mesh_components}, "
                              f"{self.mesh_min_faces})")
         self.last_components = None
+        # --mesh_simplify C: vertex clustering of the (filtered) predicted mesh on a C^3 grid over the box; 0 is off
+        self.mesh_simplify = int(getattr(config, "mesh_simplify", 0) or 0)
+        if self.mesh_simplify:
+            simplify.check_cells(self.mesh_simplify)
+        self.last_simplify = None
         # --render_pred: pictures of the predicted mesh (render.py); 'none' renders nothing
         self.render_pred = getattr(config, "render_pred", "none") or "none"
         if self.render_pred not in RENDER_VIEWS:
@@ -232,13 +237,16 @@ class LIST:
         return [pred_mesh, occ, vox_feat[0].squeeze(1)], score
 
     def filter_mesh(self, verts, faces):
-        """The mesh as marching_cubes left it on the device, without the components --mesh_components /
-        --mesh_min_faces drop (components.keep_components; its info lands in self.last_components).  With both at 0
-        the tensors come back untouched."""
-        if not (self.mesh_components or self.mesh_min_faces):
-            return verts, faces
-        verts, faces, self.last_components = components.keep_components(
-            verts, faces, keep=self.mesh_components or "all", min_faces=self.mesh_min_faces)
+        """The mesh as marching_cubes left it on the device, first without the components --mesh_components /
+        --mesh_min_faces drop (components.keep_components on the full-resolution mesh; its info lands in
+        self.last_components), then simplified on the --mesh_simplify grid (simplify.simplify; its info lands in
+        self.last_simplify).  With all three at 0 the tensors come back untouched."""
+        if self.mesh_components or self.mesh_min_faces:
+            verts, faces, self.last_components = components.keep_components(
+                verts, faces, keep=self.mesh_components or "all", min_faces=self.mesh_min_faces)
+        if self.mesh_simplify:
+            verts, faces, self.last_simplify = simplify.simplify(verts, faces, self.mesh_simplify, self.bb_min,
+                                                                 self.bb_max)
         return verts, faces
 
     def eval(self, pred, gt):

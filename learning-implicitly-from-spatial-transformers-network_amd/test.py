@@ -8,7 +8,10 @@ query grid with the HIP path and extract the iso-surface on the GPU (mesh.marchi
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py ...    # query axis sharded over GPUs
 
 `--refine_stride s` (2, 4, 8) queries the coarse-to-fine grid of refine.py instead of every grid point: the stride-s
-lattice and the fine points near the surface, the rest interpolated (`--refine_band` sets how near).  `--save_volume`
+lattice and the fine points near the surface, the rest interpolated (`--refine_band` sets how near).
+`--mesh_components K` / `--mesh_min_faces N` drop floating fragments (components.py) and `--mesh_simplify C` then merges
+the vertices of every cell of a C^3 grid over the box (simplify.py: vertex clustering on the device); what is saved is
+what is rendered and scored.  `--save_volume`
 also writes the [res,res,res] SDF volume (<stem>_sdf.npy; with --refine_stride the filled one).  `--render_pred view|canonical|both`
 renders the mesh on the device (render.py) from the model's own camera over the input image (<stem>_pred_view.png) and / or
 along the three array axes (<stem>_pred_x.png, _y, _z), at `--render_size` pixels a side.  `--eval_pred` scores
@@ -97,7 +100,7 @@ def test_all(config, save_volume=None, eval_pred=None):
             if save_volume:
                 np.save(stem + "_sdf.npy", volume.cpu().numpy())
             t0 = time.time()
-            executor.last_components = None
+            executor.last_components = executor.last_simplify = None
             m = mesh.Mesh(*executor.filter_mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5)))
             dt = time.time() - t0
             m.export(stem + "_pred.obj")
@@ -112,6 +115,10 @@ def test_all(config, save_volume=None, eval_pred=None):
             cc = executor.last_components
             if cc is not None:
                 print(f"  components: {cc['K']} found, {len(cc['kept'])} kept, {cc['dropped_faces']} faces dropped")
+            sp = executor.last_simplify
+            if sp is not None:
+                print(f"  simplified on {config.mesh_simplify}^3 cells: {len(sp['vertex_map'])} vertices in {sp['clusters']} "
+                      f"clusters, {sp['degenerate_faces']} faces collapsed")
             if eval_pred:
                 gt = batch.get("gt_mesh")
                 if gt is None:
