@@ -31,31 +31,46 @@ def _t(a):
 
 
 def _second_gap(v, f, p):
-    """The gap between the nearest and the second-nearest face distance of every point (float64, brute force)."""
+    """The gap between the nearest and the second-nearest face distance of every point: every face's distance as
+    signed_distance_cpu measures it for that face alone (fp32 d2, one sqrt; an invalid face is infinitely far), all
+    faces of a chunk of points at once."""
     from list_amd import prepare as P
-    d = np.empty((len(p), len(f)))
+    v, f, p = np.asarray(v, np.float32), np.asarray(f, np.int32).reshape(-1, 3), np.asarray(p, np.float32)
+    if len(f) < 2:
+        return np.full(len(p), np.inf)
     ok = np.all((f >= 0) & (f < len(v)), axis=1)
-    for j in range(len(f)):
-        if not ok[j]:
-            d[:, j] = np.inf
-            continue
-        ff = np.zeros((1, 3), np.int32) + f[j]
-        d[:, j] = np.abs(P.signed_distance_cpu(v, ff, p)[0])
-    d.sort(axis=1)
-    return d[:, 1] - d[:, 0] if d.shape[1] > 1 else np.full(len(p), np.inf)
+    t = v[np.where(ok[:, None], f, 0)]
+    a, b, c = ([t[None, :, j, k] for k in range(3)] for j in range(3))
+    ab, ac, bc = ([y[k] - x[k] for k in range(3)] for x, y in ((a, b), (a, c), (b, c)))
+    n = (ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0])
+    flat = (n[0] == 0) & (n[1] == 0) & (n[2] == 0)
+    gap = np.empty(len(p))
+    chunk = max(1, (1 << 19) // len(f))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for s in range(0, len(p), chunk):
+            px, py, pz = (p[s:s + chunk, k:k + 1] for k in range(3))
+            d2 = P._tri_d2(px, py, pz, a, b, c, ab, ac)
+            e = np.minimum(np.minimum(P._seg_d2(px, py, pz, a, ab), P._seg_d2(px, py, pz, a, ac)),
+                           P._seg_d2(px, py, pz, b, bc))
+            d2 = np.where(flat, e, d2)
+            d2 = np.where(ok[None, :] & ~np.isnan(d2), d2, np.float32(np.inf))
+            d = np.partition(np.sqrt(d2).astype(np.float64), 1, axis=1)
+            gap[s:s + chunk] = d[:, 1] - d[:, 0]
+    return gap
 
 
-def _check_sdf(v, f, p, check_faces=True):
+def _check_sdf(v, f, p, check_faces=True, ref=None):
+    """ref: (sdf, face_idx, winding, second gap) of signed_distance_cpu for these points, when the caller shares it."""
     P = _P()
     sdf, fi, w = P.signed_distance(_t(v), _t(f), _t(p), with_winding=True)
     sdf, fi, w = sdf.cpu().numpy(), fi.cpu().numpy(), w.cpu().numpy()
-    rs, rf, rw = P.signed_distance_cpu(v, f, p, with_winding=True)
+    rs, rf, rw = ref[:3] if ref else P.signed_distance_cpu(v, f, p, with_winding=True)
     np.testing.assert_allclose(np.abs(sdf), np.abs(rs), rtol=1e-6, atol=1e-7)
     np.testing.assert_allclose(w, rw, atol=1e-4)
     far = np.abs(rw - 0.5) > 1e-3
     np.testing.assert_array_equal(np.sign(sdf[far]), np.sign(rs[far]))
     if check_faces:
-        sep = _second_gap(v, f, p) > 1e-6
+        sep = (ref[3] if ref else _second_gap(v, f, p)) > 1e-6
         np.testing.assert_array_equal(fi[sep], rf[sep])
     return sdf, fi, w
 
@@ -73,6 +88,33 @@ def test_signed_distance_icosphere(Q, sub):
         np.testing.assert_allclose(sdf.cpu().numpy()[sel], rs, rtol=1e-6, atol=1e-7)
         return
     _check_sdf(v, f, p, check_faces=len(f) <= 400)
+
+
+# list_data_signed_distance: R = 4 when ceil(Q / 1024) >= 1024, else R = 2 when ceil(Q / 512) >= 1024, else R = 1
+SDF_BORDERS = {523_776: 1, 523_777: 2, 1_047_552: 2, 1_047_553: 4}
+
+
+@pytest.fixture(scope="module")
+def border_reference():
+    """The 20-face icosphere, max(SDF_BORDERS) points and their host answers, computed once: a border Q takes a prefix."""
+    from list_amd import evaluate as E
+    v, f = icosphere(0, 0.35)
+    p = E.box_samples_cpu(max(SDF_BORDERS), -0.6, 0.6, 7).astype(np.float32)
+    return v, f, p, _P().signed_distance_cpu(v, f, p, with_winding=True) + (_second_gap(v, f, p),)
+
+
+@pytest.mark.parametrize("Q", sorted(SDF_BORDERS))
+def test_signed_distance_dispatch_borders(border_reference, Q):
+    """sdf_kernel<R> where R changes: Q = 523 776 -> R = 1 and 1 047 552 -> R = 2 (2046 full workgroups each),
+    523 777 -> R = 2 and 1 047 553 -> R = 4 (1024 workgroups, the last with one point and every other slot past Q).
+    |sdf|, winding, sign and face index of every point."""
+    assert (4 if -(-Q // 1024) >= 1024 else 2 if -(-Q // 512) >= 1024 else 1) == SDF_BORDERS[Q]
+    v, f, p, ref = border_reference
+    sdf, fi, w = _check_sdf(v, f, p[:Q], ref=tuple(r[:Q] for r in ref))
+    assert sdf.shape == fi.shape == w.shape == (Q,)
+    gap = ref[3][:Q]
+    # a point nearest to an edge or a corner has two faces at the same distance: the face is checked on the others
+    assert np.count_nonzero(gap > 1e-6) > Q // 4 and np.count_nonzero(ref[0][:Q] < 0) > Q // 50
 
 
 def test_signed_distance_single_face_and_odd_tiles():
