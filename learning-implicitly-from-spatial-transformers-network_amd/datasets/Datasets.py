@@ -13,10 +13,18 @@
                    (with config.augment = "hip" and a training augmentation configured, the file-backed training items
                    carry 'rgb_image' as the file's uint8 [S,S,3] pixels: the executor augments the batch on the device)
 
+  Pix3D            the reference's second dataset (Datasets.py:307-497): real images of every size under
+                   {data_dir}/data/img/<cat>/<model_folder>/<img>.npy, brought to img_res x img_res with Pillow's bilinear
+                   resize; items {'rgb_image', 'points', 'values', 'occ', 'pc' [coarse_point_density,3]}
+                   (with config.augment = "hip" the training items carry 'rgb_image' as the file's uint8 [H,W,3] pixels,
+                   of different sizes: `collate` packs them into a resize.RaggedImages and the executor flips, jitters and
+                   resizes the batch on the device)
+
 The reference's names IM2SDF / IM2PointFarthest pick the file-backed form when the split lists exist under the
 configured directories and the synthetic one otherwise.  HDF5 needs h5py (not in this image); every `*.h5` path
 falls back to a `*.npz` with the same keys, which is also what the tests use.
 """
+import json
 import os
 import random
 
@@ -298,3 +306,126 @@ def IM2SDF(config, status="train"):
 
 def IM2PointFarthest(config, status="train"):
     return FileIM2PointFarthest(config, status) if _has_splits(config, status) else SyntheticIM2PointFarthest(config, status)
+
+
+# ---- Pix3D ---------------------------------------------------------------------------------------------------------
+class Pix3D(data.Dataset):
+    """Datasets.py:307-497.  Layout under config.data_dir:
+        splits/{train,test}.json                        a list of image names; 'val' reads 'test', names holding 'flipped'
+                                                        are skipped, the id is the integer of the basename
+        data/pix3d.json                                 the metadata records, indexed by id ('category', 'img', 'model')
+        data/img/<cat>/<model_folder>/<img>.npy         uint8 [H,W,3], any size
+        data/sampled_points/<cat>/<model_folder>/sampled_points.h5    query_points_sigma_* [M,4], grid_points [G,3]
+        data/isosurface/<cat>/<model_folder>/{mesh_org.ply, isosurf_scaled.obj}
+    with model_folder = '<folder>.<stem>' of the record's model path.  An item is listed when all four files exist."""
+    ragged_images = True          # train.py: batches go through `collate`
+
+    def __init__(self, config, mode="train"):
+        self.rng = np.random.RandomState(333)              # Datasets.py:314
+        self.config, self.mode = config, mode
+        self.coarse_points = config.coarse_point_density
+        self.vox_res = config.vox_res
+        self.img_res = config.img_res
+        self.occ_dtype = _occ_dtype(config)
+        self.query_samples = np.rint(np.asarray(config.sample_distribution) * config.sample_point_density).astype(np.uint32)
+        self.sigmas = config.sigmas
+        self._kdtree = None
+        split = "test" if mode == "val" else mode
+        with open(os.path.join(config.data_dir, "splits", split + ".json")) as f:
+            ids = [int(os.path.basename(name).split(".")[0]) for name in json.load(f) if "flipped" not in name]
+        self.data_path = os.path.join(config.data_dir, "data")
+        with open(os.path.join(self.data_path, "pix3d.json")) as f:
+            metadatas = json.load(f)
+        self.datalist, self.skipped = [], 0
+        for i in ids:
+            metadata = metadatas[i]
+            if metadata["category"] not in config.catlist:
+                continue
+            _, cat, img = metadata["img"].split("/")
+            model_folder = ".".join(os.path.splitext(metadata["model"])[0].split("/")[-2:])
+            info = self._paths(cat, model_folder, os.path.splitext(img)[0])
+            if not all(_exists_h5(p) if p.endswith(".h5") else os.path.exists(p) for p in info.values()):
+                self.skipped += 1
+                continue
+            info.update(sample_id=i, cat_id=metadata["category"], shape_id=model_folder, img_id=img)
+            self.datalist.append(info)
+        self.datasize = len(self.datalist)
+        print(f"{self.skipped}/{len(ids)} missing samples")
+        print(type(self).__name__, f"dataset. Finished loading the {split} dataset: {self.datasize} data.")
+
+    def _paths(self, cat, model_folder, img_name):
+        d = self.data_path
+        return {"img_path": os.path.join(d, "img", cat, model_folder, str(img_name) + ".npy"),
+                "query_path": os.path.join(d, "sampled_points", cat, model_folder, "sampled_points.h5"),
+                "mesh_path_orig": os.path.join(d, "isosurface", cat, model_folder, "mesh_org.ply"),
+                "mesh_path_norm": os.path.join(d, "isosurface", cat, model_folder, "isosurf_scaled.obj")}
+
+    def __len__(self):
+        return self.datasize
+
+    create_occ = FileIM2SDF.create_occ                     # the KD-tree over the vox_res^3 grid, and the cache next to
+    _occupancy = FileIM2SDF._occupancy                     # sampled_points.h5 (occupancies.h5)
+
+    @staticmethod
+    def _pixels(fn):
+        a = np.load(fn)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise ValueError(f"{fn}: expected a uint8 image [H,W,3] (got {a.dtype} {a.shape})")
+        return a
+
+    def _image(self, fn, train):
+        """The reference's transforms (Datasets.py:330-344): in training the flip and the colour jitter when configured,
+        then T.Resize((img_res, img_res)) = Image.resize(..., BILINEAR) and T.ToTensor().  With config.augment = "hip" a
+        training image is returned as it is in the file, uint8 [H,W,3], and nothing is drawn: the resize itself is the
+        work the executor does on the device (resize.apply)."""
+        from .. import augment, resize
+        a = self._pixels(fn)
+        if train and _augment_mode(self.config) == "hip":
+            return torch.from_numpy(a)
+        if train and getattr(self.config, "random_h_flip", False) and random.random() < 0.5:
+            a = a[:, ::-1]
+        if train and getattr(self.config, "color_jitter", False):
+            a = augment.jitter_pil(a, augment.draw_jitter(random))
+        return augment.to_tensor(resize.resize_pil(a, self.img_res))
+
+    def _cloud(self, f):
+        pc = f["grid_points"][:]
+        return np.asarray(pc[self.rng.randint(0, pc.shape[0], self.coarse_points)], dtype=np.float32)
+
+    def __getitem__(self, index):
+        d = self.datalist[index]
+        f = _Arrays(d["query_path"])
+        samples = []
+        for i, num in enumerate(self.query_samples):       # per sigma the index draw, then the grid_points choice
+            qdf = f["query_points_sigma_" + str(self.sigmas[i])]
+            samples.extend(qdf[self.rng.randint(0, qdf.shape[0], num)])
+        samples = np.asarray(samples, dtype=np.float32)
+        pc = self._cloud(f)
+        f.close()
+        return {"rgb_image": self._image(d["img_path"], self.mode == "train"),
+                "points": torch.from_numpy(samples[:, :3].copy()), "values": torch.from_numpy(samples[:, 3].copy()),
+                "occ": torch.from_numpy(self._occupancy(d["query_path"], pc).astype(self.occ_dtype)),
+                "pc": torch.from_numpy(pc)}
+
+    def get_testdata(self, cat, model_folder, img_name):
+        paths = self._paths(cat, model_folder, img_name)
+        f = _Arrays(paths["query_path"])
+        pc = self._cloud(f)
+        f.close()
+        return {"rgb_image": self._image(paths["img_path"], False).unsqueeze(0), "gt_mesh": paths["mesh_path_norm"],
+                "pc": torch.from_numpy(pc)}
+
+
+def collate(items):
+    """The DataLoader's collate_fn for datasets whose items may carry raw images: when the items' 'rgb_image' are uint8
+    [H,W,3] tensors (config.augment = "hip") they are packed into one resize.RaggedImages, whatever their sizes, and the
+    other keys are collated as usual; any other batch is default_collate's."""
+    from torch.utils.data import default_collate
+    first = items[0]
+    if not (isinstance(first, dict) and isinstance(first.get("rgb_image"), torch.Tensor)
+            and first["rgb_image"].dtype == torch.uint8):
+        return default_collate(items)
+    from .. import resize
+    batch = default_collate([{k: v for k, v in it.items() if k != "rgb_image"} for it in items])
+    batch["rgb_image"] = resize.RaggedImages.pack([it["rgb_image"] for it in items])
+    return batch

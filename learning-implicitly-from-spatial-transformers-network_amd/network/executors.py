@@ -4,7 +4,7 @@ network.models.X <-> network.executors.X (train.py of the reference, line 242)."
 import numpy as np
 import torch
 
-from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, render, s2loss, simplify, utils
+from .. import augment, chamfer, components, evaluate, mesh, parallel, refine as RF, render, resize, s2loss, simplify, utils
 from . import losses as L
 
 
@@ -22,14 +22,20 @@ def chamfer_distance(x, y):
 class _TrainImages:
     """The 'rgb_image' of a training batch on the device.  A uint8 [B,H,W,3] batch (--augment hip: the datasets hand out
     the files' pixels) is flipped, jittered and converted there in one launch (augment.apply), with parameters drawn per
-    batch from a generator seeded once per process (per rank); a float batch is copied as it is."""
+    batch from a generator seeded once per process (per rank); a float batch is copied as it is.  A resize.RaggedImages
+    (images of different sizes, from Datasets.collate) is also resized there to img_res x img_res (resize.apply), behind the
+    flip and the jitter of the same draws."""
 
     def __init__(self, config):
         self.flip = bool(getattr(config, "random_h_flip", False))
         self.jitter = bool(getattr(config, "color_jitter", False))
+        self.img_res = int(getattr(config, "img_res", 224))
         self.generator = torch.Generator().manual_seed(333 + parallel.world_info()[0])
 
     def __call__(self, img, dev):
+        if isinstance(img, resize.RaggedImages):
+            params = augment.draw_params(len(img), self.flip, self.jitter, self.generator)
+            return resize.apply(img.to(dev), self.img_res, self.img_res, params)
         if img.dtype != torch.uint8:
             return img.to(dev)
         return augment.apply(img.to(dev), augment.draw_params(img.shape[0], self.flip, self.jitter, self.generator))
@@ -63,7 +69,9 @@ class CoarseNet:
         return pred, {"chamfer_loss": self.calc_loss(pred, gt) if calc_loss else []}
 
     def test(self, batch, eval_pred=False):
-        img, gt = batch
+        img, gt = (batch["rgb_image"], batch["pc"]) if isinstance(batch, dict) else batch       # Pix3D hands out a dict
+        if gt.dim() == 2:
+            gt = gt.unsqueeze(0)
         pred = self.model(img.to(self._device())).detach().cpu()
         return pred, (self.eval(pred, gt) if eval_pred else {})
 

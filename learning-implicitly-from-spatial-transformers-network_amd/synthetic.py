@@ -105,3 +105,77 @@ def make_mlp_weights(seed, feature_size=3610, h_dim=256):
         w[name + ".weight"] = uniform(seed + 4000 + 2 * i, (fout, fin, 1), -bound, bound)
         w[name + ".bias"] = uniform(seed + 4001 + 2 * i, (fout,), -bound, bound)
     return w
+
+
+# ---------------------------------------------------------------------------
+# A tiny dataset in Pix3D's on-disk layout (datasets.Datasets.Pix3D)
+# ---------------------------------------------------------------------------
+PIX3D_SIZES = ((37, 53), (64, 48), (120, 31), (16, 16), (301, 2), (90, 140))     # (H, W) of the generated images, in turn
+_CUBE = (np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], np.float32),
+         np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4],
+                   [1, 5, 7], [1, 7, 3]]))
+_OCTAHEDRON = (np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float32),
+               np.array([[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]]))
+
+
+def _write_obj(path, verts, faces):
+    with open(path, "w") as f:
+        f.writelines(f"v {x:.6f} {y:.6f} {z:.6f}\n" for x, y, z in verts.tolist())
+        f.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in faces.tolist())
+
+
+def _write_ply(path, verts, faces):
+    with open(path, "w") as f:
+        f.write(f"ply\nformat ascii 1.0\nelement vertex {len(verts)}\nproperty float x\nproperty float y\nproperty float z\n"
+                f"element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n")
+        f.writelines(f"{x:.6f} {y:.6f} {z:.6f}\n" for x, y, z in verts.tolist())
+        f.writelines(f"3 {a} {b} {c}\n" for a, b, c in faces.tolist())
+
+
+def make_pix3d_tree(root, n_images=6, categories=("chair", "table"), sigmas=(0.003, 0.01, 0.07), rows=(60, 75, 90),
+                    grid_points=400, seed=0):
+    """Writes a tiny dataset in Pix3D's layout under `root` (= config.data_dir) and returns its description.
+
+    Two models, one per category (a cube 'chair' and an octahedron 'table', each with mesh_org.ply and isosurf_scaled.obj
+    and a sampled_points.npz stand-in holding query_points_sigma_* [rows,4] and grid_points [grid_points,3]); `n_images`
+    images uint8 [H,W,3] of the sizes PIX3D_SIZES in turn, alternating between the models; metadata records
+    data/pix3d.json for them plus one record whose files are missing; splits/train.json and splits/test.json, each naming
+    every record and one 'flipped' name that a reader must skip.  Returns {'data_dir', 'records' (the metadata list),
+    'images' {id: uint8 array}, 'missing_id', 'model_folders' {category: folder}}."""
+    import json
+    import os
+    data = os.path.join(root, "data")
+    models = {}
+    for ci, (cat, (verts, faces)) in enumerate(zip(categories, (_CUBE, _OCTAHEDRON))):
+        folder = f"SYN_{cat}_{ci:02d}.model"
+        models[cat] = folder
+        iso = os.path.join(data, "isosurface", cat, folder)
+        pts = os.path.join(data, "sampled_points", cat, folder)
+        os.makedirs(iso, exist_ok=True)
+        os.makedirs(pts, exist_ok=True)
+        os.makedirs(os.path.join(data, "img", cat, folder), exist_ok=True)
+        _write_ply(os.path.join(iso, "mesh_org.ply"), verts * np.float32(0.8 + 0.3 * ci), faces)
+        _write_obj(os.path.join(iso, "isosurf_scaled.obj"), verts * np.float32(0.3), faces)
+        tables = {f"query_points_sigma_{s}": normalish(seed + 8100 + 10 * ci + i, (rows[i], 4), 0.1) for i, s in enumerate(sigmas)}
+        tables["grid_points"] = uniform(seed + 8200 + ci, (grid_points, 3), -0.3, 0.3)
+        np.savez(os.path.join(pts, "sampled_points.npz"), **tables)
+    records, images = [], {}
+    for i in range(n_images):
+        cat = categories[i % len(categories)]
+        folder = models[cat]
+        H, W = PIX3D_SIZES[i % len(PIX3D_SIZES)]
+        images[i] = (uniform(seed + 8300 + i, (H, W, 3)) * 256).astype(np.uint8)
+        np.save(os.path.join(data, "img", cat, folder, f"{i:04d}.npy"), images[i])
+        records.append({"img": f"img/{cat}/{i:04d}.png", "category": cat,
+                        "model": f"model/{cat}/{folder.split('.')[0]}/model.obj"})
+    missing = len(records)                                   # its model has no files
+    records.append({"img": f"img/{categories[0]}/{missing:04d}.png", "category": categories[0],
+                    "model": f"model/{categories[0]}/SYN_absent/model.obj"})
+    with open(os.path.join(data, "pix3d.json"), "w") as f:
+        json.dump(records, f)
+    os.makedirs(os.path.join(root, "splits"), exist_ok=True)
+    names = [f"img/{r['category']}/{i:04d}.png" for i, r in enumerate(records)]
+    for split in ("train", "test"):
+        with open(os.path.join(root, "splits", split + ".json"), "w") as f:
+            json.dump(names + [f"img/{categories[0]}/0000_flipped.png"], f)
+    return {"data_dir": root, "records": records, "images": images, "missing_id": missing, "model_folders": models}

@@ -52,6 +52,15 @@ def write_scores(path, rows):
     return mean
 
 
+def test_items(dataset):
+    """What is tested when no test list is given: every entry of a dataset whose `datalist` carries 'img_id' (Pix3D; the
+    camera id is the image's stem, as in the reference's test.py), else the first two synthetic items."""
+    entries = getattr(dataset, "datalist", None) or []
+    if entries and all("img_id" in d for d in entries):
+        return [{"cat_id": d["cat_id"], "shape_id": d["shape_id"], "cam_id": d["img_id"].split(".")[0]} for d in entries]
+    return [{"cat_id": "synthetic", "shape_id": f"{i:04d}", "cam_id": i} for i in range(min(len(dataset), 2))]
+
+
 def test_all(config, save_volume=None, eval_pred=None):
     save_volume = getattr(config, "save_volume", False) if save_volume is None else save_volume
     eval_pred = getattr(config, "eval_pred", False) if eval_pred is None else eval_pred
@@ -72,8 +81,7 @@ def test_all(config, save_volume=None, eval_pred=None):
     executor = utils.get_class(config.model.replace("model", "executor"))(config, model)
     dataset = utils.get_class(config.dataset)(config, "test")
     out_dir = utils.ensure_dir(config.results_dir + "test_objs/")
-    items = config.testlist or [{"cat_id": "synthetic", "shape_id": f"{i:04d}", "cam_id": i}
-                                for i in range(min(len(dataset), 2))]
+    items = config.testlist or test_items(dataset)
     rank0 = (not dist.is_initialized()) or dist.get_rank() == 0
     scores = {}                                          # cat -> [(ID, score)]
     for it in items:

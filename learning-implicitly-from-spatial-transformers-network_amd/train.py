@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(_HERE))
 import list_amd                                          # noqa: E402
 from list_amd import arguments, utils                   # noqa: E402
+from list_amd.datasets import Datasets                  # noqa: E402
 
 import torch                                             # noqa: E402
 import torch.distributed as dist                         # noqa: E402
@@ -137,7 +138,9 @@ def train(config):
     sampler = torch.utils.data.distributed.DistributedSampler(trainset) if world > 1 else None
     train_iter = torch.utils.data.DataLoader(trainset, batch_size=config.train_batch_size,
                                              shuffle=sampler is None, sampler=sampler,
-                                             num_workers=config.num_workers, drop_last=True)
+                                             num_workers=config.num_workers, drop_last=True,
+                                             # Pix3D's raw images differ in size (--augment hip): one packed batch
+                                             collate_fn=Datasets.collate if getattr(trainset, "ragged_images", False) else None)
     optimizer = torch.optim.Adam(model.parameters(), lr=config.lr,
                                  betas=(config.beta1, 0.999), weight_decay=config.weight_decay)
     epoch, best_train = 0, 1e3
