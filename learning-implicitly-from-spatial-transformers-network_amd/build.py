@@ -1,7 +1,7 @@
 """Build csrc/liblist_hip.so (the C-ABI library of include/list_hip.h, list_mesh.h, list_eval.h, list_data.h, list_loss.h,
 list_refine.h, list_voxenc.h, list_coarse.h, list_imgenc.h, list_s2loss.h, list_augment.h, list_resize.h,
-list_components.h, list_render.h and list_simplify.h; csrc/list_host.h is the host-side plumbing their fifteen translation units share,
-csrc/list_cub.h the hipCUB calls of the five that scan or sort) for gfx950 with hipcc.
+list_components.h, list_render.h, list_simplify.h and list_objtext.h; csrc/list_host.h is the host-side plumbing their sixteen translation units
+share, csrc/list_cub.h the hipCUB calls of the six that scan or sort) for gfx950 with hipcc.
 
 In-tree build: the .so sits next to the sources so it travels with the repository snapshot.
 """
@@ -18,11 +18,14 @@ SOURCES = ["prep_kernels.hip", "gather_kernels.hip", "gather_box_kernels.hip", "
            "bwd_scatter_kernels.hip", "bwd_box_kernels.hip", "list_capi.hip",
            "mesh_kernels.hip", "eval_kernels.hip", "data_kernels.hip", "loss_kernels.hip",
            "refine_kernels.hip", "voxenc_kernels.hip", "coarse_kernels.hip", "imgenc_kernels.hip", "s2loss_kernels.hip",
-           "augment_kernels.hip", "resize_kernels.hip", "components_kernels.hip", "render_kernels.hip", "simplify_kernels.hip"]
+           "augment_kernels.hip", "resize_kernels.hip", "components_kernels.hip", "render_kernels.hip", "simplify_kernels.hip",
+           "objtext_kernels.hip"]
 HEADERS = ["list_common.h", "list_host.h", "list_cub.h", "point_math.h", "gather_math.h", "mfma_common.h", "box_partition.h", "mc_tables.h",
-           "stage_prep.h", "s2loss_math.h", "augment_math.h", "augment_check.h", "resize_math.h", "render_math.h", "simplify_math.h"]
+           "stage_prep.h", "s2loss_math.h", "augment_math.h", "augment_check.h", "resize_math.h", "render_math.h", "simplify_math.h",
+           "objtext_math.h", "objtext_tables.h"]
 PUBLIC_HEADERS = ["list_hip.h", "list_mesh.h", "list_eval.h", "list_data.h", "list_loss.h", "list_refine.h", "list_voxenc.h",
-                  "list_coarse.h", "list_imgenc.h", "list_s2loss.h", "list_augment.h", "list_resize.h", "list_components.h", "list_render.h", "list_simplify.h"]
+                  "list_coarse.h", "list_imgenc.h", "list_s2loss.h", "list_augment.h", "list_resize.h", "list_components.h", "list_render.h", "list_simplify.h",
+                  "list_objtext.h"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
 ARCH = "gfx950"
 

@@ -1,4 +1,4 @@
-// hipCUB's two-phase calls, shared by the units that scan or sort (mesh, refine, components, eval, simplify): the scratch size
+// hipCUB's two-phase calls, shared by the units that scan or sort (mesh, refine, components, eval, simplify, objtext): the scratch size
 // query that a layout makes, and the run on the carved scratch region.  Not part of the C ABI.
 //
 // A query returns false with the unit's error text set (LIST_ERR_HIP); a run returns LIST_OK or the HIP error under

@@ -217,7 +217,7 @@ ERR_ARG, ERR_SHAPE, ERR_WORKSPACE, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 class Section:
     """One header of the C ABI on load()'s handle: its table of exports (name -> (restype, argtypes)) and the name of
     its *_last_error symbol.  mesh.py, evaluate.py, prepare.py, chamfer.py, refine.py, voxenc.py, coarse.py, imgenc.py, s2loss.py,
-    augment.py, resize.py, components.py, render.py and simplify.py hold one each."""
+    augment.py, resize.py, components.py, render.py, simplify.py and objtext.py hold one each."""
 
     def __init__(self, exports, last_error_symbol):
         self.exports, self.last_error_symbol, self._bound = exports, last_error_symbol, None

@@ -191,7 +191,7 @@ def marching_cubes_cpu(volume, level=0.0, bb_min=-0.5, bb_max=0.5):
 # ---- mesh -----------------------------------------------------------------------------------------------------------
 class Mesh:
     """vertices float32 [V,3] and faces int32 [F,3] (0-based) on the host.  Made from CUDA tensors (as marching_cubes,
-    components.keep_components and simplify.simplify return them) it also keeps those, for render()."""
+    components.keep_components and simplify.simplify return them) it also keeps those, for render() and export()."""
 
     def __init__(self, vertices, faces):
         self._device = None
@@ -210,11 +210,16 @@ class Mesh:
         return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)})"
 
     def export(self, path):
-        """Write .obj (utils.write_obj) or binary little-endian .ply, by the file's extension."""
+        """Write .obj (utils.write_obj's bytes; composed in HIP on the device the mesh was made on, objtext.write_obj,
+        else by utils.write_obj itself) or binary little-endian .ply, by the file's extension."""
         ext = os.path.splitext(path)[1].lower()
         if ext == ".obj":
-            from . import utils
-            utils.write_obj(path, self.vertices, self.faces)
+            if self._device is not None:
+                from . import objtext
+                objtext.write_obj(path, *self._device)
+            else:
+                from . import utils
+                utils.write_obj(path, self.vertices, self.faces)
         elif ext == ".ply":
             head = ("ply\nformat binary_little_endian 1.0\n"
                     f"element vertex {len(self.vertices)}\nproperty float x\nproperty float y\nproperty float z\n"

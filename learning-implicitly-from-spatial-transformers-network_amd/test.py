@@ -111,8 +111,11 @@ def test_all(config, save_volume=None, eval_pred=None):
             executor.last_components = executor.last_simplify = None
             m = mesh.Mesh(*executor.filter_mesh(*mesh.marching_cubes(volume, 0.0, -0.5, 0.5)))
             dt = time.time() - t0
+            t0 = time.time()
             m.export(stem + "_pred.obj")
-            print(f"  mesh: {len(m.vertices)} vertices, {len(m.faces)} faces in {dt * 1e3:.1f} ms -> {stem}_pred.obj")
+            dt_obj = time.time() - t0
+            print(f"  mesh: {len(m.vertices)} vertices, {len(m.faces)} faces in {dt * 1e3:.1f} ms -> {stem}_pred.obj "
+                  f"({os.path.getsize(stem + '_pred.obj')} bytes written in {dt_obj * 1e3:.1f} ms)")
             if getattr(config, "render_pred", "none") != "none":
                 t0 = time.time()
                 views = executor.render_views(batch, m)
