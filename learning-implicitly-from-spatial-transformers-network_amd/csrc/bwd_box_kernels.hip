@@ -33,12 +33,10 @@
 
 namespace list {
 
-constexpr int kAdjPts = 64;                       // points per workgroup
+// (kAdjPts = 64 points per workgroup, kAdjC = 128 channels and the fp16 image's scale kWinPkScale: vox_adjoint_plan.h)
 constexpr int kAdjRows = 128;                     // box rows (8 tiles of 16: two per wave)
 constexpr int kAdjChunkPts = 8;                   // points staged per chunk (two K-steps)
-constexpr int kAdjC = 128;
 constexpr int kAdjNT = kAdjC / 16;                // 16-channel tiles
-constexpr float kAdjPkScale = 0.0625f;            // = kWinPkScale of bwd_scatter_kernels.hip (asserted by the launcher)
 constexpr int kAdjRowBytes = 2 * kAdjC;                                  // 256: one 16-bit plane of a staged row
 constexpr int kAdjStageRows = kAdjChunkPts * LIST_N_STENCIL;             // 56
 constexpr int kAdjPlaneBytes = kAdjStageRows * kAdjRowBytes;             // 14336
@@ -62,7 +60,7 @@ __device__ __forceinline__ int64_t adj_voxel(const RunDims& d, const ListVoxLeve
 // sequence of a K-step and the flush.  Runs, tiles, lane roles and the weights' arithmetic are the kernel's. -----------
 
 // fp16 dX.  A = dX^T: the rows are copied to LDS as they lie in memory ([sample][128 halfs]).  The finished box goes
-// through LDS once more ([row][128 halfs] at the window scale kAdjPkScale) so that the flush is the one
+// through LDS once more ([row][128 halfs] at the window scale kWinPkScale) so that the flush is the one
 // k_scatter_vox_win has: packed-half atomics into img16, the level's zeroed fp16 image, lanes over channel pairs, whole
 // 256-B rows per instruction.
 // F32OUT (diagnostic, LIST_SCATTER_F32=1): the accumulators go straight to the level's zeroed fp32 gradient as float
@@ -149,8 +147,8 @@ template <int F32OUT> struct AdjF16 {
 #pragma unroll
       for (int u = 0; u < kAdjNT / 2; ++u) {
         const f32x4v c0 = acc[i][2 * u], c1 = acc[i][2 * u + 1];
-        const uint2 lo = half4_inrange(make_float4(c0[0] * kAdjPkScale, c0[1] * kAdjPkScale, c0[2] * kAdjPkScale, c0[3] * kAdjPkScale));
-        const uint2 hi = half4_inrange(make_float4(c1[0] * kAdjPkScale, c1[1] * kAdjPkScale, c1[2] * kAdjPkScale, c1[3] * kAdjPkScale));
+        const uint2 lo = half4_inrange(make_float4(c0[0] * kWinPkScale, c0[1] * kWinPkScale, c0[2] * kWinPkScale, c0[3] * kWinPkScale));
+        const uint2 hi = half4_inrange(make_float4(c1[0] * kWinPkScale, c1[1] * kWinPkScale, c1[2] * kWinPkScale, c1[3] * kWinPkScale));
         *(uint4*)(smem + L::stage + v * kAdjRowBytes + (((4 * u + q) ^ col) << 4)) = make_uint4(lo.x, lo.y, hi.x, hi.y);
       }
     }
@@ -435,21 +433,9 @@ __global__ __launch_bounds__(256, 2) void k_scatter_vox_box(ScatterParams sp, Li
   }
 }
 
-// a window level (stencil shorter than a voxel), 128 channels; fp16 dX: the packed-half flush into an fp16 image scaled
-// by kAdjPkScale (form ADJ_F16_PK) or the diagnostic fp32 flush (ADJ_F16_F32); fp32 dX: ADJ_SPLIT
-bool scatter_box_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, float pk_scale) {
-  if (gv.C != kAdjC) return false;
-  if (sp.dx_f16) {
-    if (pk_scale != kAdjPkScale) return false;
-    if ((col_off % 8) != 0 || (sp.g.Kp % 8) != 0 || (gv.image_stride % 2) != 0) return false;
-  } else {
-    if ((col_off % 4) != 0 || (sp.g.Kp % 4) != 0) return false;
-  }
-  if (gv.W > 255 || gv.H > 255 || gv.D > 255) return false;   // 8-bit coordinates in the run records
-  return (sp.g.rows % kAdjPts) == 0;
-}
-
-// img16: the level's zeroed fp16 image (fp16 dX), or null: fp32 atomics into gv.data
+// a window level (stencil shorter than a voxel) that scatter_box_eligible (vox_adjoint_plan.h) accepts; fp16 dX: the
+// packed-half flush into img16, the level's zeroed fp16 image scaled by kWinPkScale (form ADJ_F16_PK), or, img16 null,
+// the diagnostic fp32 flush into gv.data (ADJ_F16_F32); fp32 dX: ADJ_SPLIT
 hipError_t launch_scatter_vox_box(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, _Float16* img16,
                                   hipStream_t s) {
   const dim3 grid((unsigned)(sp.g.rows / kAdjPts));

@@ -13,6 +13,7 @@
 // sort), so every map pixel GATHERS the contributions of the <= 4 pixel cells around it and is written once.
 #include <limits.h>
 #include <string.h>
+#include <type_traits>
 
 #include "list_common.h"
 #include "point_math.h"
@@ -58,14 +59,7 @@ __device__ __forceinline__ void scatter_direct(const ScatterParams& sp, const Li
   }
 }
 
-// Persistent grid (workgroups walk the 64-row blocks).  Alone, two workgroups per CU reach the atomic rate
-// (512: 1.73 ms for the three fine levels; 128: +28 %, 64: 2.1x -- the rate is partly a per-CU issue
-// limit).  Beside other kernels (ListQueryGradArgs.aux_streams) a small grid is better for the whole: the
-// atomics of a CU fill its vector-memory queue, and every load of a neighbouring gather kernel waits behind
-// them (backward 5.92 ms with 512 workgroups, 5.57 ms with 128).
-// (re-measured in round 3 with dW0 capped at 194 registers: DESIGN 5b)
-constexpr int kDirectGrid = 512, kDirectGridForked = 128;
-
+// Persistent grid (workgroups walk the 64-row blocks; its size: direct_grid_cap, vox_adjoint_plan.h)
 template <int C, int DXH>
 __global__ __launch_bounds__(256) void k_scatter_vox(ScatterParams sp, ListVoxLevel gv, int col_off, int nblocks) {
   __shared__ Pt pts[kScatterRows];
@@ -87,34 +81,45 @@ __global__ __launch_bounds__(256) void k_scatter_vox(ScatterParams sp, ListVoxLe
 // mode never takes this form.
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
+// lanes over channel pairs; WIN: a run of k_scatter_vox_win whose box does not fit the window (T threads, the taps at
+// the window levels' scale), else k_scatter_vox_h2's block (every thread has an item, the taps at the gradient scale)
+template <int C, int T, bool WIN>
+__device__ __forceinline__ void scatter_direct_h2(const ScatterParams& sp, const ListVoxLevel& gv, int col_off,
+                                                  const Pt* __restrict__ pts, int r_begin, int r_end, int64_t row0,
+                                                  _Float16* __restrict__ img16) {
+  constexpr int CP = C / 2, per_pass = (T / CP) > 0 ? (T / CP) : 1;
+  const int tid = threadIdx.x;
+  if (WIN && tid >= per_pass * CP) return;
+  const int cp = tid % CP;
+  for (int it = r_begin * LIST_N_STENCIL + tid / CP; it < r_end * LIST_N_STENCIL; it += per_pass) {
+    const int r = it / LIST_N_STENCIL, j = it - r * LIST_N_STENCIL;
+    const Pt p = pts[r];
+    if (!p.valid) continue;
+    float x, y, z;
+    stencil_rt(p, j, x, y, z);
+    const Taps t = make_taps(x, y, z, C, gv.D, gv.H, gv.W);
+    const unsigned g2 = *(const unsigned*)((const unsigned short*)sp.dx + (row0 + r) * sp.g.Kp + col_off + j * C + 2 * cp);
+    float g0 = h2f((unsigned short)(g2 & 0xffffu)), g1 = h2f((unsigned short)(g2 >> 16));
+    if (WIN) { g0 *= kWinPkScale; g1 *= kWinPkScale; }
+    _Float16* base = img16 + (int64_t)p.b * gv.image_stride + 2 * cp;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      half2v v;
+      v.x = (_Float16)(t.w[k] * g0); v.y = (_Float16)(t.w[k] * g1);
+      __builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) half2v*)(base + t.o[k]), v);
+    }
+  }
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void k_scatter_vox_h2(ScatterParams sp, ListVoxLevel gv, int col_off, int nblocks,
                                                         _Float16* __restrict__ img16) {
   __shared__ Pt pts[kScatterRows];
-  constexpr int CP = C / 2, per_pass = 256 / CP;
-  const int tid = threadIdx.x, cp = tid % CP;
   for (int blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
     __syncthreads();
     if (threadIdx.x < kScatterRows) pts[threadIdx.x] = load_point(sp.g, blk * kScatterRows + threadIdx.x);
     __syncthreads();
-    const int64_t row0 = (int64_t)blk * kScatterRows;
-    for (int it = tid / CP; it < kScatterRows * LIST_N_STENCIL; it += per_pass) {
-      const int r = it / LIST_N_STENCIL, j = it - r * LIST_N_STENCIL;
-      const Pt p = pts[r];
-      if (!p.valid) continue;
-      float x, y, z;
-      stencil_rt(p, j, x, y, z);
-      const Taps t = make_taps(x, y, z, C, gv.D, gv.H, gv.W);
-      const unsigned g2 = *(const unsigned*)((const unsigned short*)sp.dx + (row0 + r) * sp.g.Kp + col_off + j * C + 2 * cp);
-      const float g0 = h2f((unsigned short)(g2 & 0xffffu)), g1 = h2f((unsigned short)(g2 >> 16));
-      _Float16* base = img16 + (int64_t)p.b * gv.image_stride + 2 * cp;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        half2v v;
-        v.x = (_Float16)(t.w[k] * g0); v.y = (_Float16)(t.w[k] * g1);
-        __builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) half2v*)(base + t.o[k]), v);
-      }
-    }
+    scatter_direct_h2<C, 256, false>(sp, gv, col_off, pts, 0, kScatterRows, (int64_t)blk * kScatterRows, img16);
   }
 }
 
@@ -217,39 +222,7 @@ __device__ __forceinline__ void build_near(const Pt& p, int W, int H, int D, con
   if (sub == 15) n.cell = p.valid ? (base[0] + 1) | ((base[1] + 1) << 10) | ((base[2] + 1) << 20) : -1;
 }
 
-// kWinFloats: 18432 (72 KB, two workgroups per CU) for the 16^3 level, whose runs need ~100-voxel boxes;
-// 9216 (36 KB, four per CU) for the 8^3 level
-// fp16 image of a window level: kept at the gradient scale times kWinPkScale (headroom: a coarse voxel sums
-// thousands of taps)
-constexpr float kWinPkScale = 0.0625f;
-// a run whose box does not fit the window, packed-half form: lanes over channel pairs, taps at the window scale
-template <int C, int T>
-__device__ __forceinline__ void scatter_direct_h2(const ScatterParams& sp, const ListVoxLevel& gv, int col_off,
-                                                  const Pt* __restrict__ pts, int r_begin, int r_end, int64_t row0,
-                                                  _Float16* __restrict__ img16) {
-  constexpr int CP = C / 2, per_pass = (T / CP) > 0 ? (T / CP) : 1;
-  const int tid = threadIdx.x;
-  if (tid >= per_pass * CP) return;
-  const int cp = tid % CP;
-  for (int it = r_begin * LIST_N_STENCIL + tid / CP; it < r_end * LIST_N_STENCIL; it += per_pass) {
-    const int r = it / LIST_N_STENCIL, j = it - r * LIST_N_STENCIL;
-    const Pt p = pts[r];
-    if (!p.valid) continue;
-    float x, y, z;
-    stencil_rt(p, j, x, y, z);
-    const Taps t = make_taps(x, y, z, C, gv.D, gv.H, gv.W);
-    const unsigned g2 = *(const unsigned*)((const unsigned short*)sp.dx + (row0 + r) * sp.g.Kp + col_off + j * C + 2 * cp);
-    const float g0 = h2f((unsigned short)(g2 & 0xffffu)) * kWinPkScale, g1 = h2f((unsigned short)(g2 >> 16)) * kWinPkScale;
-    _Float16* base = img16 + (int64_t)p.b * gv.image_stride + 2 * cp;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      half2v v;
-      v.x = (_Float16)(t.w[k] * g0); v.y = (_Float16)(t.w[k] * g1);
-      __builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) half2v*)(base + t.o[k]), v);
-    }
-  }
-}
-
+// kWinFloats (kWinFloatsSmall or kWinFloatsLarge) and kWinPkScale, the fp16 image's scale: vox_adjoint_plan.h
 // img16 != nullptr (fp16 operands): the window is flushed as packed halfs into a zeroed fp16 image of the level
 // (scale above) and k_h16_to_grad writes the fp32 gradient afterwards -- half the atomic bytes of the flush that
 // bounds these levels.
@@ -326,7 +299,7 @@ __global__ __launch_bounds__((C >= 128 ? C : 128)) void k_scatter_vox_win(Scatte
     r.ox = __builtin_amdgcn_readfirstlane(r.ox); r.oy = __builtin_amdgcn_readfirstlane(r.oy); r.oz = __builtin_amdgcn_readfirstlane(r.oz);
     r.nx = __builtin_amdgcn_readfirstlane(r.nx); r.ny = __builtin_amdgcn_readfirstlane(r.ny); r.nz = __builtin_amdgcn_readfirstlane(r.nz);
     if (r.direct) {
-      if (DXH && img16) scatter_direct_h2<C, T>(sp, gv, col_off, pts, r.first, r.first + r.count, row0, img16);
+      if (DXH && img16) scatter_direct_h2<C, T, true>(sp, gv, col_off, pts, r.first, r.first + r.count, row0, img16);
       else scatter_direct<C, DXH, T>(sp, gv, col_off, pts, r.first, r.first + r.count, row0, inv_s);
       continue;
     }
@@ -561,6 +534,35 @@ __global__ __launch_bounds__(256) void k_vs_scatter(ScatterParams sp, ListVoxLev
   recs[atomicAdd(&bins[cell], 1)] = r;
 }
 
+// the record ranges of the four (y, z) lines a voxel is a corner of (12 independent loads, ahead of the samples): line q
+// is (y - (q & 1), z - (q >> 1)); records [lo, mid) lie in cell x-1, [mid, hi) in cell x
+struct VoxLines { int lo[4], mid[4], hi[4]; };
+__device__ __forceinline__ VoxLines vox_lines(const ListVoxLevel& gv, int64_t vox, const int* __restrict__ ends) {
+  const int W = gv.W, H = gv.H, D = gv.D;
+  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)((vox / ((int64_t)W * H)) % D);
+  const int b = (int)(vox / ((int64_t)W * H * D));
+  VoxLines r;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int yy = y - (q & 1), zz = z - (q >> 1);
+    r.lo[q] = r.mid[q] = r.hi[q] = 0;
+    if (yy < 0 || zz < 0) continue;
+    // cells x-1 and x of this (y, z) line are adjacent bins: one contiguous run of records
+    const int bin1 = ((b * D + zz) * H + yy) * W + x;          // cell x (corner dx = 0)
+    r.mid[q] = bin1 > 0 ? ends[bin1 - 1] : 0;                  // = end of cell x-1
+    r.lo[q] = x > 0 ? (bin1 > 1 ? ends[bin1 - 2] : 0) : r.mid[q];
+    r.hi[q] = ends[bin1];
+  }
+  return r;
+}
+// weight of record s of line q at the voxel (0 past the line's end)
+__device__ __forceinline__ float vox_sample_weight(const VoxSample& r, int s, int s_mid, int s_hi, int q) {
+  const int dy = q & 1, dz = q >> 1;
+  const bool dx = s < s_mid;                                   // the sample lies in cell x-1: corner +1 in x
+  const float w = (dx ? r.fx : 1.f - r.fx) * (dy ? r.fy : 1.f - r.fy) * (dz ? r.fz : 1.f - r.fz);
+  return s >= s_hi ? 0.f : w;
+}
+
 // lanes over channels, 256 / C voxels per workgroup; 8 samples in flight per lane
 template <int C, int DXH>
 __global__ __launch_bounds__(256) void k_vs_gather(ScatterParams sp, ListVoxLevel gv, const int* __restrict__ ends,
@@ -569,28 +571,12 @@ __global__ __launch_bounds__(256) void k_vs_gather(ScatterParams sp, ListVoxLeve
   const int64_t vox = (int64_t)blockIdx.x * VPB + threadIdx.x / C;
   const int c = threadIdx.x % C;
   if (vox >= n_vox) return;
-  const int W = gv.W, H = gv.H, D = gv.D;
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)((vox / ((int64_t)W * H)) % D);
-  const int b = (int)(vox / ((int64_t)W * H * D));
   float acc = 0.f;
-  // the record ranges of the four (y, z) lines first (12 independent loads), then the samples
-  int r_lo[4], r_mid[4], r_hi[4];
+  const VoxLines ln = vox_lines(gv, vox, ends);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int yy = y - (q & 1), zz = z - (q >> 1);
-    r_lo[q] = r_mid[q] = r_hi[q] = 0;
-    if (yy < 0 || zz < 0) continue;
-    // cells x-1 and x of this (y, z) line are adjacent bins: one contiguous run of records
-    const int bin1 = ((b * D + zz) * H + yy) * W + x;          // cell x (corner dx = 0)
-    r_mid[q] = bin1 > 0 ? ends[bin1 - 1] : 0;                  // = end of cell x-1
-    r_lo[q] = x > 0 ? (bin1 > 1 ? ends[bin1 - 2] : 0) : r_mid[q];
-    r_hi[q] = ends[bin1];
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int dy = q & 1, dz = q >> 1;
-    const int s_lo = r_lo[q], s_mid = r_mid[q], s_hi = r_hi[q];
-    for (int s = s_lo; s < s_hi; s += NB) {
+    const int s_mid = ln.mid[q], s_hi = ln.hi[q];
+    for (int s = ln.lo[q]; s < s_hi; s += NB) {
       VoxSample r[NB];
 #pragma unroll
       for (int u = 0; u < NB; ++u) r[u] = recs[min(s + u, s_hi - 1)];
@@ -598,12 +584,7 @@ __global__ __launch_bounds__(256) void k_vs_gather(ScatterParams sp, ListVoxLeve
 #pragma unroll
       for (int u = 0; u < NB; ++u) g[u] = dx_at<DXH>(sp.dx, (int64_t)r[u].off + c);
 #pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const bool dx = (s + u) < s_mid;                     // the sample lies in cell x-1: corner +1 in x
-        float w = (dx ? r[u].fx : 1.f - r[u].fx) * (dy ? r[u].fy : 1.f - r[u].fy) * (dz ? r[u].fz : 1.f - r[u].fz);
-        if (s + u >= s_hi) w = 0.f;
-        acc = fmaf(w, g[u], acc);
-      }
+      for (int u = 0; u < NB; ++u) acc = fmaf(vox_sample_weight(r[u], s + u, s_mid, s_hi, q), g[u], acc);
     }
   }
   ((float*)gv.data)[vox * C + c] = acc * sp.scale[1];
@@ -621,28 +602,14 @@ __global__ __launch_bounds__(256) void k_vs_gather8(ScatterParams sp, ListVoxLev
   const int64_t vox = (int64_t)blockIdx.x * VPB + threadIdx.x / TPV;
   const int c8 = (threadIdx.x % TPV) * 8;
   if (vox >= n_vox) return;
-  const int W = gv.W, H = gv.H, D = gv.D;
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)((vox / ((int64_t)W * H)) % D);
-  const int b = (int)(vox / ((int64_t)W * H * D));
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-  int r_lo[4], r_mid[4], r_hi[4];
+  const VoxLines ln = vox_lines(gv, vox, ends);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int yy = y - (q & 1), zz = z - (q >> 1);
-    r_lo[q] = r_mid[q] = r_hi[q] = 0;
-    if (yy < 0 || zz < 0) continue;
-    const int bin1 = ((b * D + zz) * H + yy) * W + x;          // cell x (corner dx = 0)
-    r_mid[q] = bin1 > 0 ? ends[bin1 - 1] : 0;                  // = end of cell x-1
-    r_lo[q] = x > 0 ? (bin1 > 1 ? ends[bin1 - 2] : 0) : r_mid[q];
-    r_hi[q] = ends[bin1];
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int dy = q & 1, dz = q >> 1;
-    const int s_lo = r_lo[q], s_mid = r_mid[q], s_hi = r_hi[q];
-    for (int s = s_lo; s < s_hi; s += NB) {
+    const int s_mid = ln.mid[q], s_hi = ln.hi[q];
+    for (int s = ln.lo[q]; s < s_hi; s += NB) {
       VoxSample r[NB];
 #pragma unroll
       for (int u = 0; u < NB; ++u) r[u] = recs[min(s + u, s_hi - 1)];
@@ -651,9 +618,7 @@ __global__ __launch_bounds__(256) void k_vs_gather8(ScatterParams sp, ListVoxLev
       for (int u = 0; u < NB; ++u) load8<DXH>(sp.dx, (int64_t)r[u].off + c8, g[u]);
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
-        const bool dx = (s + u) < s_mid;                     // the sample lies in cell x-1: corner +1 in x
-        float w = (dx ? r[u].fx : 1.f - r[u].fx) * (dy ? r[u].fy : 1.f - r[u].fy) * (dz ? r[u].fz : 1.f - r[u].fz);
-        if (s + u >= s_hi) w = 0.f;
+        const float w = vox_sample_weight(r[u], s + u, s_mid, s_hi, q);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(w, g[u][e], acc[e]);
       }
@@ -666,7 +631,7 @@ __global__ __launch_bounds__(256) void k_vs_gather8(ScatterParams sp, ListVoxLev
 }
 
 template <int C>
-static hipError_t gather_level(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, int B,
+static hipError_t gather_level(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, int B, bool lanes8,
                                const VoxGatherBuffers& vb, hipStream_t s) {
   const int64_t n_vox = (int64_t)B * gv.D * gv.H * gv.W;
   const int nb = (int)((n_vox + kScanPerBlock - 1) / kScanPerBlock);
@@ -678,20 +643,10 @@ static hipError_t gather_level(const ScatterParams& sp, const ListVoxLevel& gv, 
   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanThreads), 0, s, vb.sums, nb);
   hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(kScanThreads), 0, s, vb.bins, (int)n_vox, vb.sums);
   hipLaunchKernelGGL(k_vs_scatter<C>, gs, dim3(256), 0, s, sp, gv, vb.keys, vb.bins, (VoxSample*)vb.recs, col_off);
-  if ((col_off % 8) == 0 && (sp.g.Kp % 8) == 0 && (reinterpret_cast<uintptr_t>(gv.data) & 15) == 0) {
-    constexpr int VPB8 = 256 / (C / 8);
-    const dim3 g8((unsigned)((n_vox + VPB8 - 1) / VPB8));
-    if (sp.dx_f16)
-      hipLaunchKernelGGL((k_vs_gather8<C, 1>), g8, dim3(256), 0, s, sp, gv, vb.bins, (const VoxSample*)vb.recs, n_vox);
-    else
-      hipLaunchKernelGGL((k_vs_gather8<C, 0>), g8, dim3(256), 0, s, sp, gv, vb.bins, (const VoxSample*)vb.recs, n_vox);
-    return hipGetLastError();
-  }
-  const dim3 gg((unsigned)((n_vox + 256 / C - 1) / (256 / C)));
-  if (sp.dx_f16)
-    hipLaunchKernelGGL((k_vs_gather<C, 1>), gg, dim3(256), 0, s, sp, gv, vb.bins, (const VoxSample*)vb.recs, n_vox);
-  else
-    hipLaunchKernelGGL((k_vs_gather<C, 0>), gg, dim3(256), 0, s, sp, gv, vb.bins, (const VoxSample*)vb.recs, n_vox);
+  const int vpb = lanes8 ? 256 / (C / 8) : 256 / C;             // voxels per workgroup
+  const dim3 gg((unsigned)((n_vox + vpb - 1) / vpb));
+  auto kernel = lanes8 ? (sp.dx_f16 ? k_vs_gather8<C, 1> : k_vs_gather8<C, 0>) : (sp.dx_f16 ? k_vs_gather<C, 1> : k_vs_gather<C, 0>);
+  hipLaunchKernelGGL(kernel, gg, dim3(256), 0, s, sp, gv, vb.bins, (const VoxSample*)vb.recs, n_vox);
   return hipGetLastError();
 }
 
@@ -718,62 +673,12 @@ __global__ __launch_bounds__(256) void k_scatter_vox1(ScatterParams sp, ListVoxL
   }
 }
 
-// LIST_SCATTER_BOX (environment, read once): which window levels take the matrix-core adjoint -- 0 neither, 1 the 8^3
-// level, 3 the 16^3 level, 2 both; unset (-1): the 16^3 level, and the 8^3 level when the call is not forked
-static int scatter_box_mode() {
-  static const int mode = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e ? atoi(e) : -1; }();
-  return mode;
-}
-// LIST_SCATTER_F32=1 (environment, read once; diagnostic for the tests): the window levels flush fp32 atomics (both
-// kernels) instead of packed halfs
-static bool scatter_f32_diagnostic() {
-  static const bool on = [] { const char* e = getenv("LIST_SCATTER_F32"); return e && e[0] == '1'; }();
-  return on;
-}
-
-// stencil displacement in voxels of the level's longest axis; a window level: wide channels and a stencil shorter than
-// a voxel (the LDS-window kernel or the matrix-core adjoint)
-static float stencil_reach(const ListVoxLevel& gv) {
-  const int big = gv.W > gv.H ? (gv.W > gv.D ? gv.W : gv.D) : (gv.H > gv.D ? gv.H : gv.D);
-  return kDisp * 0.5f * (float)(big - 1);
-}
-static bool is_window_level(const ListVoxLevel& gv) { return gv.C >= 64 && stencil_reach(gv) < 0.99f; }
-
 template <int C, int kWinFloats>
 static void launch_scatter_vox_win(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s, _Float16* img16) {
   constexpr int T = C >= 128 ? C : 128;
   const dim3 grid((unsigned)(sp.g.rows / kScatterRows));
   if (sp.dx_f16) hipLaunchKernelGGL((k_scatter_vox_win<C, 1, kWinFloats>), grid, dim3(T), 0, s, sp, gv, col_off, img16);
   else hipLaunchKernelGGL((k_scatter_vox_win<C, 0, kWinFloats>), grid, dim3(T), 0, s, sp, gv, col_off, (_Float16*)nullptr);
-}
-
-template <int C>
-static hipError_t scatter_level(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, hipStream_t s,
-                                _Float16* img16 = nullptr) {
-  if constexpr (C >= 64) {
-    if (is_window_level(gv)) {
-      const bool small_box = stencil_reach(gv) < 0.34f;         // 8^3: small boxes, four window workgroups per CU
-      // 128 channels: on the matrix cores (k_scatter_vox_box).  16^3: alone 0.52 -> 0.24 ms, forked step 6.63 -> 6.29 ms.
-      // 8^3: alone 0.28 -> 0.12 ms; beside the other streams of the forked backward the VALU kernel is the better
-      // neighbour (2 waves of 199 registers per workgroup against 4 of 243: step +0.05 ms with the matrix-core form), so
-      // forked calls keep it unless LIST_SCATTER_BOX=2
-      const int box_mode = scatter_box_mode();
-      const bool box = small_box ? (box_mode < 0 ? !sp.forked : (box_mode == 1 || box_mode == 2))
-                                 : (box_mode < 0 || box_mode == 2 || box_mode == 3);
-      // fp16 dX: into the fp16 image, or (diagnostic) fp32 atomics; fp32 dX (bf16x3, bf16): bf16 hi + lo operands
-      if (box && (sp.dx_f16 ? (img16 || scatter_f32_diagnostic()) : !img16) && scatter_box_eligible(sp, gv, col_off, kWinPkScale))
-        return launch_scatter_vox_box(sp, gv, col_off, img16, s);
-      if (small_box) launch_scatter_vox_win<C, 9216>(sp, gv, col_off, s, img16);
-      else launch_scatter_vox_win<C, 18432>(sp, gv, col_off, s, img16);
-      return hipGetLastError();
-    }
-  }
-  const int nblocks = sp.g.rows / kScatterRows;
-  const int cap = sp.forked ? kDirectGridForked : kDirectGrid;
-  const dim3 pgrid((unsigned)(nblocks < cap ? nblocks : cap));
-  if (sp.dx_f16) hipLaunchKernelGGL((k_scatter_vox<C, 1>), pgrid, dim3(256), 0, s, sp, gv, col_off, nblocks);
-  else hipLaunchKernelGGL((k_scatter_vox<C, 0>), pgrid, dim3(256), 0, s, sp, gv, col_off, nblocks);
-  return hipGetLastError();
 }
 
 // packed-half atomics: zero the level's fp16 image, run `scatter` into it, then one pass to the fp32 gradient
@@ -792,103 +697,79 @@ static hipError_t scatter_via_h16(const ScatterParams& sp, const ListVoxLevel& g
   return hipGetLastError();
 }
 
-hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
-                              const ListVoxLevel grad_vox[LIST_N_VOX_LEVELS], const VoxGatherBuffers& vb,
-                              const ScatterStreams& st) {
-  (void)a;
+// f(std::integral_constant<int, C>) where C is one of Cs, the channel counts a form's kernels exist for
+template <int... Cs, class F>
+static hipError_t with_channels(int C, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((C == Cs ? (e = f(std::integral_constant<int, Cs>()), true) : false) || ...);
+  return e;
+}
+
+// executes plan_vox_adjoint (vox_adjoint_plan.h: which form, which stream, which flush -- nothing is decided here)
+hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, const ListVoxLevel grad_vox[LIST_N_VOX_LEVELS],
+                              const VoxGatherBuffers& vb, const ScatterStreams& st) {
+  // LIST_SCATTER_BOX and LIST_SCATTER_F32: environment, read once
+  static const int box_mode = [] { const char* e = getenv("LIST_SCATTER_BOX"); return e ? atoi(e) : -1; }();
+  static const bool f32_diagnostic = [] { const char* e = getenv("LIST_SCATTER_F32"); return e && e[0] == '1'; }();
   const int B = (int)((sp.g.p_begin + sp.g.n_valid + sp.g.N - 1) / sp.g.N);
-  int n_win_pk = 0, n_win_seen = 0;
+  const VoxCall c = {sp.g.n_valid, sp.g.rows, B, sp.g.Kp, sp.dx_f16 != 0, sp.forked != 0, vb.mode, vb.bins != nullptr,
+                     vb.h16 ? vb.h16_bytes : 0, vb.h16w ? vb.h16w_bytes : 0, box_mode, f32_diagnostic};      // (VoxCall's order)
+  VoxChoice plan[LIST_N_VOX_LEVELS];
+  plan_vox_adjoint(c, grad_vox, L.vox_off, plan);
+  const hipStream_t lanes[4] = {st.gather, st.direct, st.window, st.window2};      // by VoxLane
+  const int nblocks = sp.g.rows / kScatterRows, cap = direct_grid_cap(c.forked);
+  const dim3 pgrid((unsigned)(nblocks < cap ? nblocks : cap));                       // the direct forms' persistent grid
   for (int l = 0; l < LIST_N_VOX_LEVELS; ++l) {
+    const VoxChoice& p = plan[l];
+    if (p.form == VOX_SKIP) continue;
     const ListVoxLevel& gv = grad_vox[l];
-    if (!gv.data) continue;
-    hipError_t e = hipSuccess;
-    // voxel-side gather where the samples are dense enough: at least kVoxGatherMinDensity samples per cell
-    const int64_t n_vox = (int64_t)B * gv.D * gv.H * gv.W;
-    const bool window_level = is_window_level(gv);
-    const bool dense = vb.mode == 2 || (vb.mode == 0 && !window_level &&
-                                         (double)sp.g.n_valid * LIST_N_STENCIL >= kVoxGatherMinDensity * (double)n_vox);
-    if (vb.bins && dense && n_vox <= kVoxGatherMaxBins && (gv.C == 16 || gv.C == 32 || gv.C == 64 ||
-                                                                           gv.C == 128 || gv.C == 256)) {
-      switch (gv.C) {
-        case 16: e = gather_level<16>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
-        case 32: e = gather_level<32>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
-        case 64: e = gather_level<64>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
-        case 128: e = gather_level<128>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
-        default: e = gather_level<256>(sp, gv, L.vox_off[l], B, vb, st.gather); break;
-      }
-      if (e != hipSuccess) return e;
-      continue;
-    }
-    // the first window level shares its stream with dW0; the second one has a stream to itself (st.window2: the
-    // library's own side stream when the backward is forked, else the caller's).  With both behind the (contended) 2-ms
-    // dW0 the window stream ended 0.4 ms after the other two (forked backward 5.16 -> 4.98 ms with the second one behind
-    // the gathers on the caller's stream); on its own stream the training step is the same with the synthetic camera
-    // and 0.17 - 0.22 ms shorter with the points on the clamp, where the gathers ahead of it are the long ones
-    // (profiles/r04b_window_streams_ab.txt, which also has the first level on its own stream: +1.4 ms; with the 16^3 level
-    // on the matrix cores the other orders were measured again -- both levels on window2, the 16^3 level behind the
-    // gathers: +0.08 / +0.4 ms, profiles/r04b_box_adjoint.txt)
-    hipStream_t s = st.direct;
-    if (window_level && vb.mode != 2) { s = n_win_seen == 0 ? st.window : st.window2; ++n_win_seen; }
-    // packed-half atomics (see k_scatter_vox_h2): fp16 operands, automatic form choice, C = 32 or a non-window C = 64
-    // level, and the level's fp16 image fits the scratch the caller set aside
-    {
-      const size_t n_elem = (size_t)B * gv.image_stride;
-      if (sp.dx_f16 && vb.mode == 0 && !window_level && (gv.C == 32 || gv.C == 64) && vb.h16 &&
-          n_elem * 2 <= vb.h16_bytes && n_elem % 8 == 0 && gv.image_stride == (int64_t)gv.D * gv.H * gv.W * gv.C) {
-        e = scatter_via_h16(sp, gv, (_Float16*)vb.h16, n_elem, 1.f, s, [&](_Float16* img) {
-          const int nblocks = sp.g.rows / kScatterRows;
-          const int cap = sp.forked ? kDirectGridForked : kDirectGrid;
-          const dim3 pgrid((unsigned)(nblocks < cap ? nblocks : cap));
-          if (gv.C == 32)
-            hipLaunchKernelGGL(k_scatter_vox_h2<32>, pgrid, dim3(256), 0, s, sp, gv, L.vox_off[l], nblocks, img);
-          else
-            hipLaunchKernelGGL(k_scatter_vox_h2<64>, pgrid, dim3(256), 0, s, sp, gv, L.vox_off[l], nblocks, img);
-          return hipSuccess;
-        });
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-    // window levels, fp16 operands: packed-half flush into the level's fp16 image (its own scratch slot: the window
-    // levels run beside the direct ones), then one pass to fp32
-    if (window_level && sp.dx_f16 && vb.mode == 0 && (gv.C == 64 || gv.C == 128 || gv.C == 256) && vb.h16w && !scatter_f32_diagnostic()) {
-      const size_t n_elem = (size_t)B * gv.image_stride;
-      const size_t slot = vb.h16w_bytes / 2 / 256 * 256;         // two window levels at most share the scratch
-      char* img = (char*)vb.h16w + (size_t)(n_win_pk & 1) * slot;
-      if (n_elem * 2 <= slot && n_elem % 8 == 0 && n_win_pk < 2 &&
-          gv.image_stride == (int64_t)gv.D * gv.H * gv.W * gv.C) {
-        ++n_win_pk;
-        e = scatter_via_h16(sp, gv, (_Float16*)img, n_elem, 1.f / kWinPkScale, s, [&](_Float16* img16) {
-          switch (gv.C) {
-            case 64: return scatter_level<64>(sp, gv, L.vox_off[l], s, img16);
-            case 128: return scatter_level<128>(sp, gv, L.vox_off[l], s, img16);
-            default: return scatter_level<256>(sp, gv, L.vox_off[l], s, img16);
-          }
-        });
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-    e = hipMemsetAsync((void*)gv.data, 0, (size_t)B * gv.image_stride * sizeof(float), s);
-    if (e != hipSuccess) return e;
-    if (gv.C == 1) {
-      const int nb1 = (int)(((int64_t)sp.g.n_valid * 64 + 255) / 256);
-      const int cap1 = 4 * (sp.forked ? kDirectGridForked : kDirectGrid);
-      const dim3 grid((unsigned)(nb1 < cap1 ? nb1 : cap1));
-      if (sp.dx_f16) hipLaunchKernelGGL(k_scatter_vox1<1>, grid, dim3(256), 0, s, sp, gv, L.vox_off[l]);
-      else hipLaunchKernelGGL(k_scatter_vox1<0>, grid, dim3(256), 0, s, sp, gv, L.vox_off[l]);
-      e = hipGetLastError();
-    } else {
-      switch (gv.C) {
-        case 4: e = scatter_level<4>(sp, gv, L.vox_off[l], s); break;
-        case 8: e = scatter_level<8>(sp, gv, L.vox_off[l], s); break;
-        case 16: e = scatter_level<16>(sp, gv, L.vox_off[l], s); break;
-        case 32: e = scatter_level<32>(sp, gv, L.vox_off[l], s); break;
-        case 64: e = scatter_level<64>(sp, gv, L.vox_off[l], s); break;
-        case 128: e = scatter_level<128>(sp, gv, L.vox_off[l], s); break;
-        case 256: e = scatter_level<256>(sp, gv, L.vox_off[l], s); break;
+    const int col_off = L.vox_off[l];
+    const hipStream_t s = lanes[p.lane];
+    // the form's launches; img16: the level's zeroed fp16 image (the packed-half flushes), else null
+    auto form = [&](_Float16* img16) -> hipError_t {
+      switch (p.form) {
+        case VOX_GATHER8: case VOX_GATHER1:
+          return with_channels<16, 32, 64, 128, 256>(gv.C, [&](auto cc) {
+            return gather_level<decltype(cc)::value>(sp, gv, col_off, c.B, p.form == VOX_GATHER8, vb, s);
+          });
+        case VOX_DIRECT_H2:
+          return with_channels<32, 64>(gv.C, [&](auto cc) {
+            hipLaunchKernelGGL(k_scatter_vox_h2<decltype(cc)::value>, pgrid, dim3(256), 0, s, sp, gv, col_off, nblocks, img16);
+            return hipSuccess;
+          });
+        case VOX_BOX: return launch_scatter_vox_box(sp, gv, col_off, img16, s);
+        case VOX_WINDOW:
+          return with_channels<64, 128, 256>(gv.C, [&](auto cc) {
+            constexpr int C = decltype(cc)::value;
+            if (p.win_floats == kWinFloatsSmall) launch_scatter_vox_win<C, kWinFloatsSmall>(sp, gv, col_off, s, img16);
+            else launch_scatter_vox_win<C, kWinFloatsLarge>(sp, gv, col_off, s, img16);
+            return hipGetLastError();
+          });
+        case VOX_DIRECT:
+          return with_channels<4, 8, 16, 32, 64, 128, 256>(gv.C, [&](auto cc) {
+            constexpr int C = decltype(cc)::value;
+            hipLaunchKernelGGL((sp.dx_f16 ? k_scatter_vox<C, 1> : k_scatter_vox<C, 0>), pgrid, dim3(256), 0, s, sp, gv, col_off, nblocks);
+            return hipGetLastError();
+          });
+        case VOX_SCALAR: {
+          const int nb1 = (int)(((int64_t)sp.g.n_valid * 64 + 255) / 256), cap1 = 4 * cap;
+          const dim3 grid((unsigned)(nb1 < cap1 ? nb1 : cap1));
+          hipLaunchKernelGGL((sp.dx_f16 ? k_scatter_vox1<1> : k_scatter_vox1<0>), grid, dim3(256), 0, s, sp, gv, col_off);
+          return hipGetLastError();
+        }
         default: return hipErrorInvalidValue;
       }
+    };
+    const size_t n_elem = (size_t)c.B * gv.image_stride;
+    char* const slot1 = (char*)vb.h16w + h16w_slot_bytes(c.h16w_bytes);
+    hipError_t e = hipSuccess;
+    switch (p.flush) {
+      case VOX_FLUSH_H16: e = scatter_via_h16(sp, gv, (_Float16*)vb.h16, n_elem, 1.f, s, form); break;
+      case VOX_FLUSH_H16W0: e = scatter_via_h16(sp, gv, (_Float16*)vb.h16w, n_elem, 1.f / kWinPkScale, s, form); break;
+      case VOX_FLUSH_H16W1: e = scatter_via_h16(sp, gv, (_Float16*)slot1, n_elem, 1.f / kWinPkScale, s, form); break;
+      case VOX_FLUSH_F32: e = hipMemsetAsync((void*)gv.data, 0, n_elem * sizeof(float), s);   // (also ahead of an invalid level)
+        [[fallthrough]];
+      case VOX_FLUSH_STORE: if (e == hipSuccess) e = form(nullptr);
     }
     if (e != hipSuccess) return e;
   }
@@ -1343,10 +1224,9 @@ __global__ __launch_bounds__(256) void k_trans_grad(ScatterParams sp, const void
 }
 
 hipError_t launch_img_grad(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
-                           const int* bins_pix, int nslots, void* recs, float* grad_img_map, int map_f16,
+                           const int* bins_pix, void* recs, float* grad_img_map, int map_f16,
                            float* grad_trans_mat, void* const* stage_events, hipStream_t s, void* heavy,
                            size_t heavy_bytes) {
-  (void)nslots;
   const int ms = a.map_size, Ct = L.img_C;
   ImgRec* rc = (ImgRec*)recs;
   auto mark = [&](int stage) {

@@ -1121,7 +1121,7 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
     LIST_TRY(hipEventCreateWithFlags(&ev_dw0, hipEventDisableTiming), "event");
     LIST_TRY(hipEventRecord(ev_dw0, s_window), "event");
   }
-  LIST_TRY(launch_scatter_vox(sp, L, *a, ga->grad_vox, vb, sst), "voxel scatter launch");
+  LIST_TRY(launch_scatter_vox(sp, L, ga->grad_vox, vb, sst), "voxel scatter launch");
   mark(LIST_BWD_VOX);
   if (a->percep_feat) {
     if (ga->grad_percep_feat)
@@ -1150,7 +1150,7 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   // for tools/trans_noise_probe2.py)
   static const bool unordered = [] { const char* e = getenv("LIST_BWD_TRANS_UNORDERED"); return e && e[0] == '1'; }();
   const bool split = forked && ga->grad_trans_mat && !unordered;
-  LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, nslots, bwp + bw.recs, ga->grad_img_map, map_f16,
+  LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, bwp + bw.recs, ga->grad_img_map, map_f16,
                            split ? nullptr : ga->grad_trans_mat, ga->stage_events, s, bwp + bw.img_heavy,
                            bw.img_heavy_bytes), "image gradient launch");
   if (ga->grad_img_levels)
@@ -1160,7 +1160,7 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
     // ... on aux_streams[2] where there is one (idle once the 8^3 window level is done; s_win2 is `s` otherwise)
     // instead of at the end of `s`: training step 6.43 -> 6.36 ms, 6.52 -> 6.32 with the points on the clamp
     if (ev_dw0) LIST_TRY(hipStreamWaitEvent(s_win2, ev_dw0, 0), "stream order");
-    LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, nslots, bwp + bw.recs, nullptr, map_f16, ga->grad_trans_mat,
+    LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, bwp + bw.recs, nullptr, map_f16, ga->grad_trans_mat,
                              ga->stage_events, s_win2, nullptr, 0), "trans_mat gradient launch");
   }
   if (ev_dw0) { (void)hipEventDestroy(ev_dw0); ev_dw0 = nullptr; }
@@ -1213,7 +1213,7 @@ int list_percep_pool_bwd(const ListPoolGradArgs* ga, void* stream) {
   sp.g.perm0 = 0; sp.g.perm1 = 1; sp.g.perm2 = 2; sp.g.scale = 1.f;
   sp.g.N = a->N; sp.g.p_begin = 0; sp.g.n_valid = (int)P; sp.g.rows = (int)rows; sp.g.Kp = a->img_C;
   sp.dx = dx; sp.dx_f16 = 0; sp.scale = scale;
-  e = launch_img_grad(sp, L, q, nullptr, 0, recs, ga->grad_img_map, 0, ga->grad_trans_mat, nullptr, s);
+  e = launch_img_grad(sp, L, q, nullptr, recs, ga->grad_img_map, 0, ga->grad_trans_mat, nullptr, s);
   if (e != hipSuccess) return hip_fail(e, "percep_pool_bwd launch");
   return LIST_OK;
 }

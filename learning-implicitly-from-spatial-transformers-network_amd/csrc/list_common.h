@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "list_hip.h"
+#include "vox_adjoint_plan.h"       // kDisp (the stencil displacement) and what chooses a voxel level's adjoint form
 
 namespace list {
 
@@ -51,7 +52,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 constexpr int kRowTile = 256;       // GEMM BM: workspace rows are padded to this
 constexpr int kKTile = 64;          // GEMM BK (largest): feature columns are padded to this
 constexpr int kGatherRows = 64;     // query points per gather workgroup
-constexpr float kDisp = 0.0722f;    // stencil displacement, network/modules.py:205
 
 // ---- bf16 hi/lo split -------------------------------------------------------------------
 // hi = bf16_rne(x), lo = bf16_rne(x - hi): x ~ hi + lo to 16 significant bits.
@@ -530,26 +530,22 @@ struct ScatterParams {
   int forked;                 // the adjoint forms run side by side on auxiliary streams
 };
 // buffers of the voxel-side gather (bwd_scatter_kernels.hip); bins == nullptr disables it
-constexpr int64_t kVoxGatherMaxBins = 4194304;      // cells (B * D * H * W) a level may have
-constexpr double kVoxGatherMinDensity = 2.0;         // samples per cell
 // mode: ListQueryGradArgs.vox_adjoint; h16 / h16w: scratch for the fp16 image of a direct level / of the two window
 // levels (packed-half atomics), or null
 struct VoxGatherBuffers { int* keys; int* bins; int* sums; void* recs; int mode; void* h16; size_t h16_bytes; void* h16w; size_t h16w_bytes; };
-// the three adjoint forms may run on different streams (gather / direct atomics / LDS windows)
-// matrix-core adjoint of a window level (bwd_box_kernels.hip).  fp16 dX: packed-half flush into img16, the level's zeroed
-// fp16 image at scale pk_scale, or (img16 null, diagnostic) fp32 atomics; fp32 dX: bf16 hi + lo operands, fp32 flush
-bool scatter_box_eligible(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, float pk_scale);
+// matrix-core adjoint of a window level (bwd_box_kernels.hip; scatter_box_eligible: vox_adjoint_plan.h).  fp16 dX:
+// packed-half flush into img16, the level's zeroed fp16 image at scale kWinPkScale, or (img16 null, diagnostic) fp32
+// atomics; fp32 dX: bf16 hi + lo operands, fp32 flush
 hipError_t launch_scatter_vox_box(const ScatterParams& sp, const ListVoxLevel& gv, int col_off, _Float16* img16,
                                   hipStream_t s);
-struct ScatterStreams { hipStream_t gather, direct, window, window2; };
-hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
-                              const ListVoxLevel grad_vox[LIST_N_VOX_LEVELS], const VoxGatherBuffers& vb,
-                              const ScatterStreams& st);
+struct ScatterStreams { hipStream_t gather, direct, window, window2; };     // the adjoint forms' streams (VoxLane)
+hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, const ListVoxLevel grad_vox[LIST_N_VOX_LEVELS],
+                              const VoxGatherBuffers& vb, const ScatterStreams& st);
 // map_f16: grad_img_map receives halfs at the gradient scale (the intermediate of the adjoint resize, fp16 operands)
 // heavy / heavy_bytes: scratch of the map-side gather's heavy groups (img_heavy_bytes(); null: every group is walked by
 // its own workgroup)
 hipError_t launch_img_grad(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
-                           const int* bins_pix, int nslots, void* recs, float* grad_img_map, int map_f16,
+                           const int* bins_pix, void* recs, float* grad_img_map, int map_f16,
                            float* grad_trans_mat, void* const* stage_events, hipStream_t s, void* heavy = nullptr,
                            size_t heavy_bytes = 0);
 hipError_t launch_rows_to_grad(const ScatterParams& sp, int img_off, int C, int B, int* row_of_scratch, float* out,

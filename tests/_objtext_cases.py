@@ -1,11 +1,12 @@
 """Inputs shared by test_objtext_cpu.py and test_objtext_gpu.py: the structured float32 bit patterns, the border face
 indices, the oracle (the f-string of utils.write_obj, value by value) and the host program of tests/csrc/objtext_host.cpp."""
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
 import numpy as np
+
+from _host_cxx import host_cxx
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "learning-implicitly-from-spatial-transformers-network_amd", "csrc")
@@ -126,11 +127,8 @@ def loop_file(directory, verts, faces, name="loop.obj"):
 # ---- the header on the host -------------------------------------------------------------------------------------------
 def build_host(directory):
     """Compiles tests/csrc/objtext_host.cpp with AddressSanitizer and UndefinedBehaviorSanitizer -> the program's path."""
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if c and os.path.exists(c)), None)
-    assert cxx, "no host C++ compiler found (c++, g++, clang++ or ROCm's clang++)"
     exe = os.path.join(str(directory), "objtext_host")
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+    subprocess.run([host_cxx(), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-fno-omit-frame-pointer", "-I", CSRC, os.path.join(ROOT, "tests", "csrc", "objtext_host.cpp"),
                     "-o", exe], check=True)
     return exe

@@ -1,10 +1,11 @@
 """Meshes and cameras shared by test_render_cpu.py and test_render_gpu.py, and the host program over csrc/render_math.h
 (tests/csrc/render_host.cpp).  Nothing here rasterises: the tests decide what is compared with what."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
+
+from _host_cxx import host_cxx
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "learning-implicitly-from-spatial-transformers-network_amd", "csrc")
@@ -181,11 +182,8 @@ def three_spheres(n=48):
 # ---- the header on the host ---------------------------------------------------------------------------------------------
 def build_host(directory):
     """Compiles tests/csrc/render_host.cpp for the host as the library is built (no contraction) -> the program's path."""
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if c and os.path.exists(c)), None)
-    assert cxx, "no host C++ compiler found (c++, g++, clang++ or ROCm's clang++)"
     exe = os.path.join(str(directory), "render_host")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-I", CSRC,
+    subprocess.run([host_cxx(), "-O2", "-std=c++17", "-ffp-contract=off", "-I", CSRC,
                     os.path.join(ROOT, "tests", "csrc", "render_host.cpp"), "-o", exe, "-lm"], check=True)
     return exe
 

@@ -4,10 +4,11 @@ out_faces [F',3], vertex_map [V], and the totals (clusters, invalid_verts, inval
 import fractions
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
+
+from _host_cxx import host_cxx
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "learning-implicitly-from-spatial-transformers-network_amd", "csrc")
@@ -271,11 +272,8 @@ def runs(length, before, order, seed=3):
 # ---- the header on the host ---------------------------------------------------------------------------------------------
 def build_host(directory):
     """Compiles tests/csrc/simplify_host.cpp for the host as the library is built (no contraction) -> the program's path."""
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if c and os.path.exists(c)), None)
-    assert cxx, "no host C++ compiler found (c++, g++, clang++ or ROCm's clang++)"
     exe = os.path.join(str(directory), "simplify_host")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-I", CSRC,
+    subprocess.run([host_cxx(), "-O2", "-std=c++17", "-ffp-contract=off", "-I", CSRC,
                     os.path.join(ROOT, "tests", "csrc", "simplify_host.cpp"), "-o", exe, "-lm"], check=True)
     return exe
 

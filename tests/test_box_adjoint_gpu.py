@@ -53,14 +53,17 @@ def other_process(tmp, mode, case, overlap, f32=False, precision="fp16"):
     return dict(np.load(out))
 
 
-def test_the_fp16_images_of_both_levels_fit_the_scratch_in_these_cases():
-    """(What makes a window level take the packed-half flush, hence the matrix-core kernel: bwd_scatter_kernels.hip,
-    launch_scatter_vox -- two window levels share rows x H2 halfs of scratch.)"""
-    for k in CASES.values():
-        rows = (k["batch"] * k["n"] + 255) // 256 * 256
-        slot = rows * 256 * 2 // 2 // 256 * 256
-        assert k["batch"] * 16 ** 3 * 128 * 2 <= slot
-        assert k["batch"] * 8 ** 3 * 128 * 2 <= slot
+def test_the_fp16_images_of_both_levels_fit_the_scratch_in_these_cases(tmp_path):
+    """(What makes a window level take the packed-half flush, hence the matrix-core kernel: two window levels share rows x H2
+    halfs of scratch.  The rule itself is asked -- csrc/vox_adjoint_plan.h, which launch_scatter_vox executes, through the
+    host program of tests/test_vox_adjoint_plan_cpu.py: levels 4 and 5 take a slot each, in line and forked.)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _vox_plan as VP
+    got = VP.plans(VP.build_host(tmp_path), {f"{name}_{int(forked)}": VP.case(B=k["batch"], N=k["n"], forked=forked)
+                                             for name, k in CASES.items() for forked in (False, True)})
+    assert len(got) == 2 * len(CASES)
+    for name, levels in got.items():
+        assert levels[4].endswith("/window/w0") and levels[5].endswith("/window2/w1"), (name, levels)
 
 
 @pytest.mark.parametrize("case,bound", [("one_image", 6e-3), ("two_images", 6e-3)])

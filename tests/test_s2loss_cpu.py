@@ -109,15 +109,12 @@ def test_targets_of_every_dtype_are_the_same_numbers():
 def test_the_kernels_logarithm_against_libm_on_the_host(tmp_path):
     """csrc/s2loss_math.h is plain C++: compiled for the host (no contraction into fma beyond the explicit ones, as the
     library is built) and held to libm's log at the 4 float64 ulps its header derives, with libm's non-finite cases."""
-    import shutil
     import subprocess
+    from _host_cxx import host_cxx
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"),
-                            "/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if c and os.path.exists(c)), None)
-    assert cxx, "no host C++ compiler found (c++, g++, clang++ or ROCm's clang++)"
     exe = str(tmp_path / "s2loss_log_host")
     csrc = os.path.join(root, "learning-implicitly-from-spatial-transformers-network_amd", "csrc")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-I", csrc,
+    subprocess.run([host_cxx(), "-O2", "-std=c++17", "-ffp-contract=off", "-I", csrc,
                     os.path.join(root, "tests", "csrc", "s2loss_log_host.cpp"), "-o", exe, "-lm"], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, check=True, timeout=120).stdout
     print(out)
