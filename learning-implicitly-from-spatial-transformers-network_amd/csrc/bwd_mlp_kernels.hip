@@ -306,12 +306,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_tn16(GemmTnParams p) {
   }
 }
 
-int wgrad_splits(int M, int N, int P, int terms) {
-  const int nk = P / (terms == 3 ? 32 : 64);
-  const int s = wgrad_nominal_splits(M, N);
-  return s > nk ? (nk < 1 ? 1 : nk) : s;
-}
-
 hipError_t launch_gemm_tn(const GemmTnParams& p, int terms, hipStream_t s) {
   if (p.M <= 0 || p.M % 256 || p.N < 8 || p.N % 8 || p.P <= 0 || p.P % 256 || p.splits < 1)
     return hipErrorInvalidValue;

@@ -32,8 +32,7 @@
 
 namespace list {
 
-constexpr int kBoxPts = 64;                                  // points per workgroup
-constexpr int kBoxSamples = kBoxPts * LIST_N_STENCIL;        // 448
+constexpr int kBoxSamples = kBoxPts * LIST_N_STENCIL;        // 448 (kBoxPts points per workgroup: query_fwd_plan.h)
 constexpr int kBoxMaxKeys = 512;                             // window keys a run may have
 constexpr int kBoxNb = 2;                                    // tiles per turn of a wave
 constexpr int kBoxRowsBig = 256;                             // LDS box rows, levels wider than 8 voxels
@@ -301,16 +300,6 @@ __global__ __launch_bounds__(256) void k_gather_vox_box(GatherParams g, ListVoxL
     first += count;
     if (first < kBoxPts) __syncthreads();                     // the next run overwrites the box and the lists
   }
-}
-
-// near level with fp16 maps and an fp16 feature matrix; false: not taken (the caller falls back to k_gather_vox_near)
-bool gather_box_eligible(const GatherParams& g, const ListVoxLevel& lv, int col_off) {
-  static const bool off = [] { const char* e = getenv("LIST_GATHER_BOX"); return e && e[0] == '0' && e[1] == 0; }();
-  if (off) return false;
-  if (g.fmt != FMT_FP16 || lv.dtype != LIST_MAP_F16 || lv.C != 128) return false;
-  if ((col_off % 8) != 0 || (g.Kp % 8) != 0 || (lv.image_stride % 8) != 0) return false;
-  if (lv.W > 31 || lv.H > 31 || lv.D > 31) return false;       // 5-bit cell indices in the tile records
-  return (g.rows % kBoxPts) == 0;
 }
 
 hipError_t launch_gather_vox_box(const GatherParams& g, const ListVoxLevel& lv, int col_off, hipStream_t s, int order) {

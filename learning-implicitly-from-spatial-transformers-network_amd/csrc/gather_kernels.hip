@@ -520,12 +520,10 @@ __global__ __launch_bounds__(256) void k_sort_scatter(int n_valid, const int* __
   }
 }
 
-hipError_t launch_sort_points(const GatherParams& g, const ListQueryArgs& a, const SortBuffers& sb,
+hipError_t launch_sort_points(const GatherParams& g, const ListQueryArgs& a, const SortBuffers& sb, bool img,
                               hipStream_t s) {
   SortParams sp;
   sp.b_first = (int)(g.p_begin / g.N);
-  const bool img = a.percep_feat == nullptr && sb.order_img != nullptr &&
-                   a.map_size * ((a.map_size + 3) / 4) <= kSortPixCells;
   sp.pixel = img ? 1 : 0; sp.trans_mat = a.trans_mat; sp.ms = a.map_size; sp.clamp_hi = a.clamp_hi;
   const int64_t b_last = (g.p_begin + g.n_valid - 1) / g.N;
   const int nslots = (int)((b_last - sp.b_first + 1 < kSortImages) ? (b_last - sp.b_first + 1) : kSortImages);
@@ -865,43 +863,39 @@ hipError_t launch_gather_fixup(const GatherParams& g, const FeatLayout& L, const
 // barrier (list_common.h, LIST_LAUNCH / any_order()): six drains of the chip less per chunk, 0.91 -> 0.86 ms for the
 // seven launches of the metric's shape.  `order` = 0 keeps the plain in-order launch (taken for all seven when the
 // caller asks for a stage event between two gathers: per-kernel timing).
-static bool vox_level_is_near(const ListVoxLevel& lv) {
-  const int big = lv.W > lv.H ? (lv.W > lv.D ? lv.W : lv.D) : (lv.H > lv.D ? lv.H : lv.D);
-  return kDisp * 0.5f * (float)(big - 1) < 0.99f && lv.C >= 16;           // stencil stays within one cell
-}
-
-// ride: the scalar level / xyz / padding that this level's kernel writes too (k_gather_vox only), or null
+// form: the level's entry of QueryFwdPlan.vox; ride: the scalar level / xyz / padding that a VG_PLAIN_RIDE level's kernel
+// writes too
 template <int C, int FMT, int F16>
 static hipError_t launch_vox_level_t(const GatherParams& g, const ListVoxLevel& lv, int col_off,
-                                     hipStream_t s, int order, const TailArgs* ride) {
+                                     hipStream_t s, int order, VoxGather form, const TailArgs& ride) {
   using G = VoxGeom<C, MapT<F16>::V>;
-  const bool near = vox_level_is_near(lv);
-  if (near && gather_box_eligible(g, lv, col_off)) return launch_gather_vox_box(g, lv, col_off, s, order);
-  TailArgs none;
-  memset(&none, 0, sizeof(none));
-  if (near)
-    LIST_LAUNCH((k_gather_vox_near<C, FMT, F16>), dim3(g.rows / G::RB), dim3(256), 0, s, order, g, lv, col_off);
-  else if (ride) {
-    if constexpr (C <= 64) LIST_LAUNCH((k_gather_vox<C, FMT, F16, 1>), dim3(g.rows / G::RB), dim3(256), 0, s, order, g, lv, col_off, *ride);
-    else return hipErrorInvalidValue;
-  } else
-    LIST_LAUNCH((k_gather_vox<C, FMT, F16, 0>), dim3(g.rows / G::RB), dim3(256), 0, s, order, g, lv, col_off, none);
+  const TailArgs none = {};
+  switch (form) {
+    case VG_BOX: return launch_gather_vox_box(g, lv, col_off, s, order);
+    case VG_NEAR: LIST_LAUNCH((k_gather_vox_near<C, FMT, F16>), dim3(g.rows / G::RB), dim3(256), 0, s, order, g, lv, col_off); break;
+    case VG_PLAIN: LIST_LAUNCH((k_gather_vox<C, FMT, F16, 0>), dim3(g.rows / G::RB), dim3(256), 0, s, order, g, lv, col_off, none); break;
+    case VG_PLAIN_RIDE:
+      if constexpr (C <= 64) LIST_LAUNCH((k_gather_vox<C, FMT, F16, 1>), dim3(g.rows / G::RB), dim3(256), 0, s, order, g, lv, col_off, ride);
+      else return hipErrorInvalidValue;
+      break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
 template <int C, int FMT>
 static hipError_t launch_vox_level(const GatherParams& g, const ListVoxLevel& lv, int col_off,
-                                   hipStream_t s, int order, const TailArgs* ride) {
+                                   hipStream_t s, int order, VoxGather form, const TailArgs& ride) {
   if (lv.dtype == LIST_MAP_F16) {
-    if constexpr (C >= 8) return launch_vox_level_t<C, FMT, 1>(g, lv, col_off, s, order, ride);
+    if constexpr (C >= 8) return launch_vox_level_t<C, FMT, 1>(g, lv, col_off, s, order, form, ride);
     else return hipErrorInvalidValue;
   }
-  return launch_vox_level_t<C, FMT, 0>(g, lv, col_off, s, order, ride);
+  return launch_vox_level_t<C, FMT, 0>(g, lv, col_off, s, order, form, ride);
 }
 
 template <int FMT>
 static hipError_t launch_gather_fmt(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a,
-                                    int* nan_tiles, hipStream_t s, bool skip_img) {
+                                    const QueryFwdPlan& plan, int* nan_tiles, hipStream_t s) {
   hipError_t e = hipSuccess;
   auto mark = [&](int stage) {
     if (a.stage_events && a.stage_events[stage]) (void)hipEventRecord((hipEvent_t)a.stage_events[stage], s);
@@ -915,75 +909,57 @@ static hipError_t launch_gather_fmt(const GatherParams& g, const FeatLayout& L, 
   for (int l = 0; l < LIST_N_VOX_LEVELS; ++l)
     if (a.vox[l].C == 1) { tl.lv[tl.n] = a.vox[l]; tl.off[tl.n] = L.vox_off[l]; ++tl.n; }
 
-  // The scalar level rides along with the vector level of the same grid (gather_pair, TailRide): one scalar level,
-  // fp32 in place, and a level of 8 .. 64 channels with its dimensions that takes k_gather_vox.  LIST_TAIL_RIDE=0 keeps
-  // k_gather_tail (A/B runs).
-  static const bool ride_on = [] { const char* e = getenv("LIST_TAIL_RIDE"); return !(e && e[0] == '0' && e[1] == 0); }();
-  int ride_level = -1;
-  TailArgs ride;
-  memset(&ride, 0, sizeof(ride));
-  if (ride_on && tl.n == 1 && tl.lv[0].dtype == LIST_MAP_F32) {
-    for (int l = 0; l < LIST_N_VOX_LEVELS && ride_level < 0; ++l) {
-      const ListVoxLevel& lv = a.vox[l];
-      if (lv.C >= 8 && lv.C <= 64 && lv.D == tl.lv[0].D && lv.H == tl.lv[0].H && lv.W == tl.lv[0].W && !vox_level_is_near(lv) &&
-          (int64_t)lv.D * lv.H * lv.W * lv.C < ((int64_t)1 << 31))
-        ride_level = l;
-    }
-    if (ride_level >= 0) {
-      ride.l0 = (const float*)tl.lv[0].data; ride.l0_stride = tl.lv[0].image_stride; ride.l0_off = tl.off[0];
-      ride.xyz_off = L.xyz_off; ride.F = L.F; ride.nan_tiles = nan_tiles;
-    }
+  TailArgs ride = {};                                   // what the VG_PLAIN_RIDE level's kernel writes beside its own columns
+  if (plan.ride_level >= 0) {
+    ride.l0 = (const float*)tl.lv[0].data; ride.l0_stride = tl.lv[0].image_stride; ride.l0_off = tl.off[0];
+    ride.xyz_off = L.xyz_off; ride.F = L.F; ride.nan_tiles = nan_tiles;
   }
   auto vox_level = [&](int l) -> hipError_t {
     const ListVoxLevel& lv = a.vox[l];
-    const TailArgs* rd = l == ride_level ? &ride : nullptr;
     switch (lv.C) {
-      case 4: return launch_vox_level<4, FMT>(g, lv, L.vox_off[l], s, order, rd);
-      case 8: return launch_vox_level<8, FMT>(g, lv, L.vox_off[l], s, order, rd);
-      case 16: return launch_vox_level<16, FMT>(g, lv, L.vox_off[l], s, order, rd);
-      case 32: return launch_vox_level<32, FMT>(g, lv, L.vox_off[l], s, order, rd);
-      case 64: return launch_vox_level<64, FMT>(g, lv, L.vox_off[l], s, order, rd);
-      case 128: return launch_vox_level<128, FMT>(g, lv, L.vox_off[l], s, order, rd);
-      case 256: return launch_vox_level<256, FMT>(g, lv, L.vox_off[l], s, order, rd);
+      case 4: return launch_vox_level<4, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
+      case 8: return launch_vox_level<8, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
+      case 16: return launch_vox_level<16, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
+      case 32: return launch_vox_level<32, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
+      case 64: return launch_vox_level<64, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
+      case 128: return launch_vox_level<128, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
+      case 256: return launch_vox_level<256, FMT>(g, lv, L.vox_off[l], s, order, plan.vox[l], ride);
       default: return hipErrorInvalidValue;
     }
   };
+  // k_gather_img<FMT, F16, OUT32> on `map` with Ct channels per pixel
+  auto sample = [&](auto f16, auto out32, const void* map, int Ct, int col_off, int kept) {
+    LIST_LAUNCH((k_gather_img<FMT, f16(), out32()>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, map, a.trans_mat,
+                a.map_size, Ct, a.clamp_hi, col_off, kept);
+  };
+  using I0 = std::false_type;
+  using I1 = std::true_type;
   auto img = [&]() -> hipError_t {
-    if (skip_img) return hipSuccess;      // the perceptual block is produced inside fc_0 (fused_fc0_kernels.hip)
-    if (a.percep_proj) {          // projected perceptual map: H1 channels, fp16 (fp16 operands) or fp32
-      if (FMT == FMT_FP16)
-        LIST_LAUNCH((k_gather_img<FMT, 1, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.percep_proj,
-                    a.trans_mat, a.map_size, a.H1, a.clamp_hi, 0, 0);
-      else
-        LIST_LAUNCH((k_gather_img<FMT, 0, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.percep_proj,
-                    a.trans_mat, a.map_size, a.H1, a.clamp_hi, 0, 0);
-    } else if (a.img_proj && !g.rowvec) {
-      // fc_0 samples the projected channels itself (EPI_RELU_SAMPLE): the kept channels only, in the order of the rows
-      if (FMT != FMT_FP16 || g.order_img) return hipErrorInvalidValue;
-      if (a.img_kept_C == 0) return hipSuccess;
-      LIST_LAUNCH((k_gather_img<FMT_FP16, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,
-                  a.trans_mat, a.map_size, a.img_kept_C + a.H1, a.clamp_hi, L.img_off, a.img_kept_C);
-    } else if (a.img_proj) {      // list_prep_img_proj: img_kept_C sampled channels | H1 projected ones per pixel
-      if (FMT == FMT_FP16)
-        LIST_LAUNCH((k_gather_img<FMT, 1, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,
-                    a.trans_mat, a.map_size, a.img_kept_C + a.H1, a.clamp_hi, L.img_off, a.img_kept_C);
-      else
-        LIST_LAUNCH((k_gather_img<FMT, 0, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,
-                    a.trans_mat, a.map_size, a.img_kept_C + a.H1, a.clamp_hi, L.img_off, a.img_kept_C);
-    } else if (a.percep_feat) {
-      LIST_LAUNCH(k_copy_percep<FMT>, dim3((g.rows + 255) / 256), dim3(256), 0, s, order, g,
-                  a.percep_feat, a.pf_sb, a.pf_sc, a.pf_sn, L.img_C, L.img_off);
-    } else if (a.img_dtype == LIST_MAP_F16) {
-      LIST_LAUNCH((k_gather_img<FMT, 1>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,
-                  a.trans_mat, a.map_size, L.img_C, a.clamp_hi, L.img_off, 0);
-    } else {
-      LIST_LAUNCH((k_gather_img<FMT, 0>), dim3(g.rows / kGatherRows), dim3(256), 0, s, order, g, a.img_map,
-                  a.trans_mat, a.map_size, L.img_C, a.clamp_hi, L.img_off, 0);
+    switch (plan.img) {
+      case IMG_NONE: return hipSuccess;   // the perceptual block is produced inside fc_0
+      case IMG_PROJECTED:                 // H1 channels, fp16 (fp16 operands) or fp32
+        if (FMT == FMT_FP16) sample(I1(), I1(), a.percep_proj, a.H1, 0, 0);
+        else sample(I0(), I1(), a.percep_proj, a.H1, 0, 0);
+        break;
+      case IMG_KEPT:                      // fc_0 samples the projected channels itself (EPI_RELU_SAMPLE)
+        if (FMT != FMT_FP16 || g.order_img) return hipErrorInvalidValue;
+        sample(I1(), I0(), a.img_map, a.img_kept_C + a.H1, L.img_off, a.img_kept_C);
+        break;
+      case IMG_KEPT_ROWVEC:               // list_prep_img_proj: img_kept_C sampled channels | H1 projected ones per pixel
+        if (FMT == FMT_FP16) sample(I1(), I1(), a.img_map, a.img_kept_C + a.H1, L.img_off, a.img_kept_C);
+        else sample(I0(), I1(), a.img_map, a.img_kept_C + a.H1, L.img_off, a.img_kept_C);
+        break;
+      case IMG_COPY:
+        LIST_LAUNCH(k_copy_percep<FMT>, dim3((g.rows + 255) / 256), dim3(256), 0, s, order, g,
+                    a.percep_feat, a.pf_sb, a.pf_sc, a.pf_sn, L.img_C, L.img_off);
+        break;
+      case IMG_SAMPLE_F16: sample(I1(), I0(), a.img_map, L.img_C, L.img_off, 0); break;
+      case IMG_SAMPLE_F32: sample(I0(), I0(), a.img_map, L.img_C, L.img_off, 0); break;
     }
     return hipGetLastError();
   };
   auto tail = [&]() -> hipError_t {
-    if (ride_level >= 0) return hipSuccess;           // written by the riding level's kernel
+    if (plan.ride_level >= 0) return hipSuccess;      // written by the riding level's kernel
     LIST_LAUNCH(k_gather_tail<FMT>, dim3((g.rows + 31) / 32), dim3(256), 0, s, order, g, tl, L.xyz_off, L.F, nan_tiles);
     return hipGetLastError();
   };
@@ -1034,22 +1010,10 @@ static hipError_t launch_gather_fmt(const GatherParams& g, const FeatLayout& L, 
   return hipSuccess;
 }
 
-// bit l set: voxel level l goes to the matrix-core gather (the condition launch_vox_level_t dispatches on)
-int gather_box_levels(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a) {
-  int mask = 0;
-  for (int l = 0; l < LIST_N_VOX_LEVELS; ++l) {
-    const ListVoxLevel& lv = a.vox[l];
-    const int big = lv.W > lv.H ? (lv.W > lv.D ? lv.W : lv.D) : (lv.H > lv.D ? lv.H : lv.D);
-    const bool near = kDisp * 0.5f * (float)(big - 1) < 0.99f && lv.C >= 16;
-    if (near && gather_box_eligible(g, lv, L.vox_off[l])) mask |= 1 << l;
-  }
-  return mask;
-}
-
-hipError_t launch_gather(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a,
-                         int* nan_tiles, hipStream_t s, bool skip_img) {
-  return g.fmt == FMT_FP16 ? launch_gather_fmt<FMT_FP16>(g, L, a, nan_tiles, s, skip_img)
-                           : launch_gather_fmt<FMT_BF16_SPLIT>(g, L, a, nan_tiles, s, skip_img);
+hipError_t launch_gather(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a, const QueryFwdPlan& plan,
+                         int* nan_tiles, hipStream_t s) {
+  return g.fmt == FMT_FP16 ? launch_gather_fmt<FMT_FP16>(g, L, a, plan, nan_tiles, s)
+                           : launch_gather_fmt<FMT_BF16_SPLIT>(g, L, a, plan, nan_tiles, s);
 }
 
 // ---- diagnostics: X (gather order, hi+lo) -> out[B][F][N] in the reference order ---------------------

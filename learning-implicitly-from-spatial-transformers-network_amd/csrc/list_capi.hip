@@ -13,6 +13,36 @@ constexpr int64_t kMaxChunkRows = 262144;     // bounds the workspace (~4.6 GB) 
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- rules more than one entry point checks
+int check_precision(int32_t p, const char* whose = "") {
+  return p < LIST_PREC_BF16X3 || p > LIST_PREC_FP16 ? fail(LIST_ERR_ARG, "%sprecision=%d", whose, p) : LIST_OK;
+}
+int check_hidden(int H1, int H2, int H3) {
+  if (H1 % 256 == 0 && H2 % 256 == 0 && H3 == 256 && H1 > 0 && H2 > 0) return LIST_OK;
+  return fail(LIST_ERR_UNSUPPORTED, "hidden sizes %d/%d/%d (need H1,H2 multiples of 256, H3 = 256)", H1, H2, H3);
+}
+// (a flag, not a count: anything else is a struct of another ABI version or an uninitialised one)
+int check_flag(int32_t v, const char* name) {
+  if (v == 0 || v == 1) return LIST_OK;
+  return fail(LIST_ERR_ARG, "%s=%d (0 or 1; zero-initialise ListQueryArgs, list_abi_version() = %d)", name, v, LIST_ABI_VERSION);
+}
+int check_operand_pair(int32_t precision, int32_t img_dtype, const char* who) {
+  if ((precision == LIST_PREC_FP16) == (img_dtype == LIST_MAP_F16)) return LIST_OK;
+  return fail(LIST_ERR_UNSUPPORTED, "%s: fp16 operands pair with fp16 maps, the bf16 formats with fp32 maps", who);
+}
+// split formats: the interleaved fc_0 weight (list_common.h xi_off) is the former [hi plane | lo plane] pair
+bool w0_planes_contiguous(const PackedMlp& pk, int H1, int Kp) { return pk.w0_lo == pk.w0_hi + (size_t)H1 * Kp * 2; }
+// the descriptors of an image pyramid (with_data: inputs); *Ct receives the channel total
+int check_img_levels(const ListMap2D* maps, bool with_data, const char* what, int* Ct) {
+  *Ct = 0;
+  for (int i = 0; i < LIST_N_IMG_LEVELS; ++i) {
+    const ListMap2D& m = maps[i];
+    if ((with_data && !m.data) || m.C < 1 || m.H < 1 || m.W < 1) return fail(LIST_ERR_SHAPE, "%s %d: bad descriptor", what, i);
+    *Ct += m.C;
+  }
+  return LIST_OK;
+}
+
 bool vox_in_place(const ListMap3D& m, ListVoxLevel* lv, int32_t map_dtype) {
   const int64_t C = m.C, W = m.W, H = m.H;
   lv->C = m.C; lv->D = m.D; lv->H = m.H; lv->W = m.W; lv->dtype = LIST_MAP_F32; lv->reserved_ = 0;
@@ -77,9 +107,7 @@ int check_query_common(const ListQueryArgs* a, FeatLayout* L) {
     if ((int64_t)a->map_size * a->map_size * a->img_C >= (int64_t)1 << 31)
       return fail(LIST_ERR_SHAPE, "image map larger than 2^31 elements");
   }
-  if (a->img_proj != 0 && a->img_proj != 1)
-    return fail(LIST_ERR_ARG, "img_proj=%d (0 or 1; zero-initialise ListQueryArgs, list_abi_version() = %d)", a->img_proj,
-                LIST_ABI_VERSION);
+  if (int rc = check_flag(a->img_proj, "img_proj")) return rc;
   if (a->img_proj) {
     // list_prep_img_proj's map: img_kept_C sampled channels | H1 projected ones; the row vector lives in the lo plane of
     // X (fp16 operands: unused otherwise) or behind the kept columns of the row's perceptual block (split formats)
@@ -95,8 +123,7 @@ int check_query_common(const ListQueryArgs* a, FeatLayout* L) {
                   a->img_kept_C, a->H1, a->img_C);
     if ((int64_t)a->map_size * a->map_size * (a->img_kept_C + a->H1) >= (int64_t)1 << 31)
       return fail(LIST_ERR_SHAPE, "projected map larger than 2^31 elements");
-    if ((a->precision == LIST_PREC_FP16) != (a->img_dtype == LIST_MAP_F16))
-      return fail(LIST_ERR_UNSUPPORTED, "img_proj: fp16 operands pair with fp16 maps, the bf16 formats with fp32 maps");
+    if (int rc = check_operand_pair(a->precision, a->img_dtype, "img_proj")) return rc;
   } else if (a->img_kept_C != 0) {
     return fail(LIST_ERR_ARG, "img_kept_C=%d without img_proj", a->img_kept_C);
   }
@@ -108,8 +135,7 @@ int check_query_common(const ListQueryArgs* a, FeatLayout* L) {
       return fail(LIST_ERR_UNSUPPORTED, "percep_proj needs img_C %% 64 == 0, H1 %% 8 == 0 and H1 * 4 <= img_C * %d bytes", xbytes);
     if ((int64_t)a->map_size * a->map_size * a->H1 >= (int64_t)1 << 31)
       return fail(LIST_ERR_SHAPE, "projected map larger than 2^31 elements");
-    if ((a->precision == LIST_PREC_FP16) != (a->img_dtype == LIST_MAP_F16))
-      return fail(LIST_ERR_UNSUPPORTED, "percep_proj: fp16 operands pair with fp16 maps, the bf16 formats with fp32 maps");
+    if (int rc = check_operand_pair(a->precision, a->img_dtype, "percep_proj")) return rc;
   }
   return LIST_OK;
 }
@@ -125,16 +151,18 @@ GatherParams make_gather(const ListQueryArgs* a, const FeatLayout& L, const Work
   g.Kp = L.Kp;
   g.fmt = a->precision == LIST_PREC_FP16 ? FMT_FP16 : FMT_BF16_SPLIT;
   g.order = nullptr; g.order_img = nullptr; g.row_of = nullptr;
-  // where the projected perceptual sample (H1 floats per row) goes; fc_0's epilogue reads it from there
   g.rowvec = nullptr; g.rv_stride = 0;
-  const int xb = a->precision == LIST_PREC_FP16 ? 2 : 4;
-  if (a->percep_proj) {                      // the head of the row's perceptual block
-    g.rowvec = (float*)g.x_hi; g.rv_stride = (int64_t)L.Kp * xb / 4;
-  } else if (a->img_proj) {
-    if (xb == 2) { g.rowvec = (float*)g.x_lo; g.rv_stride = a->H1; }                 // the lo plane: rows * Kp * 2 >= rows * H1 * 4
-    else { g.rowvec = (float*)g.x_hi + a->img_kept_C; g.rv_stride = (int64_t)L.Kp; }  // behind the kept columns (4 B per column)
-  }
   return g;
+}
+// where the projected perceptual sample (H1 floats per row) goes; fc_0's epilogue reads it from there
+void place_rowvec(GatherParams* g, RowvecHome home, const ListQueryArgs* a) {
+  const int xb = a->precision == LIST_PREC_FP16 ? 2 : 4;
+  switch (home) {
+    case ROWVEC_NONE: break;
+    case ROWVEC_X_HEAD: g->rowvec = (float*)g->x_hi; g->rv_stride = (int64_t)g->Kp * xb / 4; break;
+    case ROWVEC_X_LO: g->rowvec = (float*)g->x_lo; g->rv_stride = a->H1; break;
+    case ROWVEC_BEHIND_KEPT: g->rowvec = (float*)g->x_hi + a->img_kept_C; g->rv_stride = (int64_t)g->Kp; break;
+  }
 }
 
 // rows the given workspace can hold (multiple of kRowTile, capped at the request), or 0
@@ -150,65 +178,17 @@ int64_t chunk_rows_for(size_t bytes, int64_t P, int Kp, int H1, int H2) {
   return fit >= kRowTile ? fit : 0;
 }
 
-// fc_0 with the perceptual block of its A operand produced on chip (fused_fc0_kernels.hip): fp16 operands and maps,
-// the per-point 2-D sample (no pre-pooled features, no projected map), H1 = 512.  LIST_FUSED_FC0 (environment, read
-// once): "0" keeps the unfused path (2-D gather kernel + k_gemm_nt_pp), "x" runs the 128 x 512 tile with every K-tile
-// from X (tile-shape diagnostic: the 2-D gather still runs).
-int fused_fc0_mode() {
-  static const int mode = [] {
-    const char* e = getenv("LIST_FUSED_FC0");
-    if (!e || !e[0]) return 1;
-    if (e[0] == '0' && e[1] == 0) return 0;
-    if (e[0] == 'x') return 2;
-    if (e[0] == '3' && e[1] == 0) return 3;
-    return 1;
+// The forward's three environment switches, read once (QueryFwdCall has their values), and the call's plan
+QueryFwdPlan plan_for(const ListQueryArgs* a, const FeatLayout& L, int64_t rows, bool gather_only) {
+  struct Switches { int fused_fc0; bool gather_box, tail_ride; };
+  static const Switches sw = [] {
+    auto env = [](const char* name) { const char* e = getenv(name); return e ? e : ""; };
+    auto is0 = [](const char* e) { return e[0] == '0' && e[1] == 0; };
+    const char* f = env("LIST_FUSED_FC0");
+    return Switches{is0(f) ? 0 : f[0] == 'x' ? 2 : (f[0] == '3' && f[1] == 0) ? 3 : 1, !is0(env("LIST_GATHER_BOX")),
+                    !is0(env("LIST_TAIL_RIDE"))};
   }();
-  return mode;
-}
-// What the call sites ask (each its own question; the answers coincide on some paths only):
-//   runs_fc0_fused_kernel   : fc_0 is the 128 x 512 kernel (k_fc0_fused)
-//   runs_fc0_sampled        : fc_0 is the 256 x 256 ping-pong kernel with the sampling epilogue (EPI_RELU_SAMPLE), behind
-//                             the kept-channels-only 2-D gather: fp16 inference forwards on list_prep_img_proj's map
-//   fc0_samples_map         : fc_0 samples the perceptual map itself -- no row-vector buffer, no pixel order in the sort;
-//                             what list_query_plan reports as fused_fc0
-//   skips_img_gather        : no 2-D gather launch at all (every perceptual column of X is produced inside fc_0)
-bool runs_fc0_fused_kernel(const ListQueryArgs* a, const FeatLayout& L) {
-  if (fused_fc0_mode() == 0) return false;
-  if (a->percep_feat || a->percep_proj) return false;
-  // list_prep_img_proj's map leaves 2 perceptual K-tiles of 43: not worth the 128-row tile (runs_fc0_sampled, or the
-  // row-vector pair)
-  if (a->img_proj) return false;
-  // fp16 operands with fp16 maps, the bf16 formats with fp32 maps (the pairs the standard path takes too)
-  if ((a->precision == LIST_PREC_FP16) != (a->img_dtype == LIST_MAP_F16)) return false;
-  // bf16x3 keeps the unfused path: its packed weight is twice as long (hi + lo), and a 128-row tile streams ALL of it
-  // (7.3 MB per tile, 9.3 GB per 160 k points) -- measured (round 4): fc_0 1.15 -> 2.15 ms, step 3.58 -> 4.20 ms.
-  // LIST_FUSED_FC0=3 forces it (A/B runs, tests).
-  if (a->precision == LIST_PREC_BF16X3 && fused_fc0_mode() != 3) return false;
-  // inference forwards only: list_sdf_query_bwd reads the WHOLE feature matrix (d fc_0.weight = dZ1^T . X, the perceptual
-  // columns included), so a forward that a backward may follow materialises it
-  if (!a->no_activations || a->no_fused_fc0) return false;
-  return a->H1 == 512 && a->img_C > 0 && a->img_C % 64 == 0 && L.img_off == 0 && L.Kp % 64 == 0;
-}
-int fused_produced_tiles(const ListQueryArgs* a) {
-  return fused_fc0_mode() == 2 ? 0 : a->img_C / (a->precision == LIST_PREC_FP16 ? 64 : 32);
-}
-bool skips_img_gather(const ListQueryArgs* a, const FeatLayout& L) {
-  return runs_fc0_fused_kernel(a, L) && fused_fc0_mode() != 2;
-}
-bool runs_fc0_sampled(const ListQueryArgs* a, const FeatLayout& L) {
-  // (LIST_FUSED_FC0=0 / x keep the row-vector pair here too, as they keep the unfused pair on the standard path)
-  if (!a->img_proj || a->precision != LIST_PREC_FP16 || a->img_dtype != LIST_MAP_F16) return false;
-  if (fused_fc0_mode() == 0 || fused_fc0_mode() == 2 || !a->no_activations || a->no_fused_fc0) return false;
-  return a->H1 == 512 && a->img_C % 64 == 0 && L.img_off == 0 && L.Kp % 64 == 0;
-}
-bool fc0_samples_map(const ListQueryArgs* a, const FeatLayout& L) {
-  return skips_img_gather(a, L) || runs_fc0_sampled(a, L);
-}
-
-// inference forwards in fp16: fc_1, fc_2 and fc_out as ONE launch (gemm_kernels.hip, k_mlp_tail_f16).  The one
-// predicate behind the dispatch in list_sdf_query_fwd and behind list_query_plan (what a caller's accounting reads).
-bool takes_fused_tail(const ListQueryArgs* a) {
-  return a->no_activations && a->precision == LIST_PREC_FP16 && a->H2 == 256 && a->H3 == 256 && a->H1 % 64 == 0;
+  return plan_query_fwd({a, L.Kp, L.img_off, (int)rows, L.vox_off, sw.fused_fc0, sw.gather_box, sw.tail_ride, gather_only});
 }
 
 }  // namespace
@@ -236,13 +216,8 @@ int list_prep_img_maps(const ListMap2D maps[LIST_N_IMG_LEVELS], int32_t B, int32
   if (!dtype_ok(map_dtype)) return fail(LIST_ERR_ARG, "map_dtype=%d", map_dtype);
   if (B <= 0 || map_size < 2 || map_size > 320)
     return fail(LIST_ERR_SHAPE, "B=%d map_size=%d (need 2..320)", B, map_size);
-  int Ct = 0;
-  for (int i = 0; i < LIST_N_IMG_LEVELS; ++i) {
-    const ListMap2D& m = maps[i];
-    if (!m.data || m.C < 1 || m.H < 1 || m.W < 1)
-      return fail(LIST_ERR_SHAPE, "image level %d: bad descriptor", i);
-    Ct += m.C;
-  }
+  int Ct;
+  if (int rc = check_img_levels(maps, true, "image level", &Ct)) return rc;
   const int align = map_dtype == LIST_MAP_F16 ? 8 : 4;
   if (Ct % align) return fail(LIST_ERR_UNSUPPORTED, "total image channels %d not a multiple of %d", Ct, align);
   if (!aligned16(out)) return fail(LIST_ERR_SHAPE, "out must be 16-byte aligned");
@@ -329,16 +304,12 @@ int list_prep_vox_maps(const ListMap3D maps[LIST_N_VOX_LEVELS], int32_t B, int32
 // ------------------------------------------------------------------------------------------ weights
 static int weights_layout(const ListMlpWeights* w, FeatLayout* L) {
   if (!w) return fail(LIST_ERR_ARG, "weights is NULL");
-  if (w->precision < LIST_PREC_BF16X3 || w->precision > LIST_PREC_FP16)
-    return fail(LIST_ERR_ARG, "weights precision=%d", w->precision);
+  if (int rc = check_precision(w->precision, "weights ")) return rc;
   if (!w->w0 || !w->b0 || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3)
     return fail(LIST_ERR_ARG, "a weight pointer is NULL");
   if (!make_layout(w->vox_C, w->img_C, L)) return fail(LIST_ERR_UNSUPPORTED, "unsupported channel counts");
   if (L->F != w->F) return fail(LIST_ERR_SHAPE, "F=%d but channels give %d", w->F, L->F);
-  if (w->H1 % 256 || w->H2 % 256 || w->H3 != 256 || w->H1 <= 0 || w->H2 <= 0)
-    return fail(LIST_ERR_UNSUPPORTED, "hidden sizes %d/%d/%d (need H1,H2 multiples of 256, H3 = 256)",
-                w->H1, w->H2, w->H3);
-  return LIST_OK;
+  return check_hidden(w->H1, w->H2, w->H3);
 }
 
 size_t list_packed_mlp_bytes(const ListMlpWeights* w) {
@@ -399,15 +370,14 @@ int list_prep_percep_proj(const void* img_map, int32_t img_dtype, int32_t B, int
                           int32_t H1, int32_t H2, int32_t H3, int32_t precision, void* proj,
                           size_t proj_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (!img_map || !vox_C || !packed_mlp || !proj) return fail(LIST_ERR_ARG, "NULL pointer");
-  if (precision < LIST_PREC_BF16X3 || precision > LIST_PREC_FP16) return fail(LIST_ERR_ARG, "precision=%d", precision);
+  if (int rc = check_precision(precision)) return rc;
   if (B <= 0 || map_size < 2) return fail(LIST_ERR_SHAPE, "B=%d map_size=%d", B, map_size);
   FeatLayout L;
   if (!make_layout(vox_C, img_C, &L)) return fail(LIST_ERR_UNSUPPORTED, "unsupported channel counts");
   const bool fp16 = precision == LIST_PREC_FP16;
   if (img_C % 64 || H1 % 256 || H1 <= 0)
     return fail(LIST_ERR_UNSUPPORTED, "percep_proj needs img_C %% 64 == 0 and H1 %% 256 == 0 (img_C=%d, H1=%d)", img_C, H1);
-  if (fp16 != (img_dtype == LIST_MAP_F16))
-    return fail(LIST_ERR_UNSUPPORTED, "percep_proj: fp16 operands pair with fp16 maps, the bf16 formats with fp32 maps");
+  if (int rc = check_operand_pair(precision, img_dtype, "percep_proj")) return rc;
   if (!aligned16(img_map) || !aligned16(packed_mlp) || !aligned16(proj) || (scratch && !aligned16(scratch)))
     return fail(LIST_ERR_SHAPE, "buffers must be 16-byte aligned");
   if (proj_bytes < list_percep_proj_bytes(B, map_size, H1, precision))
@@ -416,7 +386,7 @@ int list_prep_percep_proj(const void* img_map, int32_t img_dtype, int32_t B, int
   if (need && (!scratch || scratch_bytes < need))
     return fail(LIST_ERR_WORKSPACE, "scratch too small: %zu < %zu", scratch_bytes, need);
   const PackedMlp pk = packed_mlp_layout(L.Kp, H1, H2, H3);
-  if (!fp16 && pk.w0_lo != pk.w0_hi + (size_t)H1 * L.Kp * 2)
+  if (!fp16 && !w0_planes_contiguous(pk, H1, L.Kp))
     return fail(LIST_ERR_ARG, "internal: hi / lo planes of the packed fc_0 weight are not contiguous");
   hipStream_t s = (hipStream_t)stream;
   const int64_t px = (int64_t)B * map_size * map_size;
@@ -451,7 +421,7 @@ struct ImgProjPlan {
 };
 int img_proj_plan(const ListMap2D* maps, int32_t B, int32_t n_kept, int32_t H1, int32_t precision, ImgProjPlan* pl) {
   if (!maps) return fail(LIST_ERR_ARG, "maps is NULL");
-  if (precision < LIST_PREC_BF16X3 || precision > LIST_PREC_FP16) return fail(LIST_ERR_ARG, "precision=%d", precision);
+  if (int rc = check_precision(precision)) return rc;
   if (B <= 0 || B > 65535) return fail(LIST_ERR_SHAPE, "B=%d", B);
   if (n_kept < 0 || n_kept >= LIST_N_IMG_LEVELS)
     return fail(LIST_ERR_ARG, "n_kept_levels=%d (need 0 .. %d: at least one level is projected)", n_kept, LIST_N_IMG_LEVELS - 1);
@@ -462,6 +432,7 @@ int img_proj_plan(const ListMap2D* maps, int32_t B, int32_t n_kept, int32_t H1, 
   auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
   for (int i = 0; i < LIST_N_IMG_LEVELS; ++i) {
     const ListMap2D& m = maps[i];
+    // (level by level with the channel rule, not check_img_levels first: the first level at fault decides the code)
     if (!m.data || m.C < 1 || m.H < 1 || m.W < 1) return fail(LIST_ERR_SHAPE, "image level %d: bad descriptor", i);
     if (m.C % 64) return fail(LIST_ERR_UNSUPPORTED, "image level %d: C=%d (img_proj needs multiples of 64)", i, m.C);
     pl->img_C += m.C;
@@ -511,7 +482,7 @@ int list_prep_img_proj(const ListMap2D maps[LIST_N_IMG_LEVELS], int32_t B, int32
   if (scratch_bytes < pl.scratch) return fail(LIST_ERR_WORKSPACE, "scratch too small: %zu < %zu", scratch_bytes, pl.scratch);
   if ((int64_t)map_size * map_size * (pl.kept_C + H1) >= (int64_t)1 << 31) return fail(LIST_ERR_SHAPE, "projected map larger than 2^31 elements");
   const PackedMlp pk = packed_mlp_layout(L.Kp, H1, H2, H3);
-  if (!fp16 && pk.w0_lo != pk.w0_hi + (size_t)H1 * L.Kp * 2)
+  if (!fp16 && !w0_planes_contiguous(pk, H1, L.Kp))
     return fail(LIST_ERR_ARG, "internal: hi / lo planes of the packed fc_0 weight are not contiguous");
   hipStream_t s = (hipStream_t)stream;
   const int Ct = pl.kept_C + H1;
@@ -580,18 +551,9 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
   if (rc != LIST_OK) return rc;
   if (!a->sdf || !a->packed_mlp) return fail(LIST_ERR_ARG, "sdf/packed_mlp is NULL");
   if (a->F != L.F) return fail(LIST_ERR_SHAPE, "F=%d but channels give %d", a->F, L.F);
-  if (a->H1 % 256 || a->H2 % 256 || a->H3 != 256 || a->H1 <= 0 || a->H2 <= 0)
-    return fail(LIST_ERR_UNSUPPORTED, "hidden sizes %d/%d/%d", a->H1, a->H2, a->H3);
-  if (a->precision != LIST_PREC_BF16X3 && a->precision != LIST_PREC_BF16 &&
-      a->precision != LIST_PREC_FP16)
-    return fail(LIST_ERR_ARG, "precision=%d", a->precision);
-  // (a flag, not a count: anything else is a struct of another ABI version or an uninitialised one)
-  if (a->no_fused_fc0 != 0 && a->no_fused_fc0 != 1)
-    return fail(LIST_ERR_ARG, "no_fused_fc0=%d (0 or 1; zero-initialise ListQueryArgs, list_abi_version() = %d)",
-                a->no_fused_fc0, LIST_ABI_VERSION);
-  if (a->no_activations != 0 && a->no_activations != 1)
-    return fail(LIST_ERR_ARG, "no_activations=%d (0 or 1; zero-initialise ListQueryArgs, list_abi_version() = %d)",
-                a->no_activations, LIST_ABI_VERSION);
+  if ((rc = check_hidden(a->H1, a->H2, a->H3)) || (rc = check_precision(a->precision)) ||
+      (rc = check_flag(a->no_fused_fc0, "no_fused_fc0")) || (rc = check_flag(a->no_activations, "no_activations")))
+    return rc;
   if (!aligned16(a->workspace)) return fail(LIST_ERR_SHAPE, "workspace must be 16-byte aligned");
   const int64_t P = (int64_t)a->B * a->N;
   const int64_t rows = chunk_rows_for(a->workspace_bytes, P, L.Kp, a->H1, a->H2);
@@ -604,6 +566,7 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
   char* wsb = (char*)a->workspace;
   const int terms = a->precision == LIST_PREC_BF16X3 ? 3 : 1;
   hipStream_t s = (hipStream_t)stream;
+  const QueryFwdPlan plan = plan_for(a, L, rows, false);      // (the same for every chunk: query_fwd_plan.h)
 
   // stage events: one set of LIST_N_STAGES per row chunk (a chunk beyond the caller's sets records nothing);
   // the gather launcher marks through the same (per-chunk) array
@@ -614,6 +577,7 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     const int n_valid = (int)((P - p0 < rows) ? (P - p0) : rows);
     const int crow = (n_valid + kRowTile - 1) / kRowTile * kRowTile;
     GatherParams g = make_gather(a, L, ws, p0, n_valid, crow);
+    place_rowvec(&g, plan.rowvec, a);
     void* const* events = chunk < sets ? a->stage_events + (size_t)chunk * LIST_N_STAGES : nullptr;
     chunk_args.stage_events = events;
     auto mark = [&](int stage) {
@@ -621,34 +585,21 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     };
     mark(LIST_STAGE_BEGIN);
     hipError_t e = hipSuccess;
-    if (!a->no_sort) {
+    if (plan.sort != SORT_NONE) {
+      const bool pixel = plan.sort == SORT_MORTON_PIXEL;
       SortBuffers sb;
-      // the pixel order serves the 2-D gather kernel (and, behind a training forward, the backward's map-side gather):
-      // a forward whose fc_0 samples the map itself (k_fc0_fused, or the sampling epilogue behind the kept-channels gather,
-      // which runs in Morton order) sorts by Morton cell only -- no projection per point, half the counters, one scan and
-      // two index arrays less
-      const bool want_pix = !fc0_samples_map(a, L);
-      sb.order = (int*)(wsb + ws.order); sb.order_img = want_pix ? (int*)(wsb + ws.order_img) : nullptr;
+      sb.order = (int*)(wsb + ws.order); sb.order_img = pixel ? (int*)(wsb + ws.order_img) : nullptr;
       sb.row_of = (int*)(wsb + ws.row_of); sb.keys = (int*)(wsb + ws.keys);
       sb.keys2 = (int*)(wsb + ws.keys2); sb.bins = (int*)(wsb + ws.bins);
-      e = launch_sort_points(g, *a, sb, s);
+      e = launch_sort_points(g, *a, sb, pixel, s);
       if (e != hipSuccess) return hip_fail(e, "sort launch");
       g.order = sb.order;
-      if (want_pix && a->percep_feat == nullptr && a->map_size * ((a->map_size + 3) / 4) <= kSortPixCells) {
-        g.order_img = sb.order_img; g.row_of = sb.row_of;
-      }
+      if (pixel) { g.order_img = sb.order_img; g.row_of = sb.row_of; }
     }
     mark(LIST_STAGE_SORT);
     int* nan_tiles = (int*)(wsb + ws.nan_tiles);
-    const bool fused0 = runs_fc0_fused_kernel(a, L);
-    const bool sampled0 = runs_fc0_sampled(a, L);
-    {
-      // sampled0: no row vectors from the 2-D gather -- it samples the kept channels only (the fix-up below still
-      // writes the row vectors of the tiles it redoes, for the gated re-run)
-      GatherParams gg = g;
-      if (sampled0) gg.rowvec = nullptr;
-      e = launch_gather(gg, L, chunk_args, nan_tiles, s, /*skip_img=*/skips_img_gather(a, L));
-    }
+    // (IMG_KEPT: no row vectors from the 2-D gather; the fix-up below still writes them for the tiles the gated re-run redoes)
+    e = launch_gather(g, L, chunk_args, plan, nan_tiles, s);
     if (e != hipSuccess) return hip_fail(e, "gather launch");
     mark(LIST_STAGE_TAIL);
 
@@ -659,26 +610,23 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     gp.a_hi = wsb + ws.x_hi; gp.a_lo = wsb + ws.x_lo;
     gp.w_hi = wp + pk.w0_hi; gp.w_lo = wp + pk.w0_lo;
     gp.bias = (const float*)(wp + pk.b0);
-    gp.M = crow; gp.N = a->H1; gp.K = L.Kp;
+    gp.M = crow; gp.N = a->H1; gp.K = plan.fc0_k;
     // bf16 split formats: X and the packed fc_0 weight hold their hi / lo halfs interleaved (list_common.h xi_off)
     gp.x3i = g.fmt == FMT_FP16 ? 0 : 1;
-    if (gp.x3i && (ws.x_lo != ws.x_hi + (size_t)rows * L.Kp * 2 || pk.w0_lo != pk.w0_hi + (size_t)a->H1 * L.Kp * 2))
+    if (gp.x3i && (ws.x_lo != ws.x_hi + (size_t)rows * L.Kp * 2 || !w0_planes_contiguous(pk, a->H1, L.Kp)))
       return fail(LIST_ERR_ARG, "internal: hi / lo planes of X or of the packed fc_0 weight are not contiguous");
-    if (a->percep_proj) {
-      // the perceptual block (the first img_C columns) is left out of the K loop; its contribution was sampled from
-      // the projected map into the head of every X row and is added in the epilogue
-      const int64_t skip = (int64_t)a->img_C * (gp.x3i ? 4 : 2);
-      gp.a_hi += skip; gp.w_hi += skip;
-      gp.K = L.Kp - a->img_C; gp.lda = L.Kp; gp.ldw = L.Kp;
-      gp.rowvec = wsb + ws.x_hi; gp.rowvec_stride = (int64_t)L.Kp * (gp.x3i ? 4 : 2);
-    } else if (a->img_proj) {
-      // the projected levels' columns (img_kept_C .. img_C of the perceptual block, which leads the rows) are left out
-      // of the K loop: their contribution is the row vector the 2-D gather sampled from the projected channels
-      const int ktile = gp.x3i ? 32 : 64;                   // columns per 128-byte K-tile
-      gp.k_gap_at = a->img_kept_C / ktile; gp.k_gap = (a->img_C - a->img_kept_C) / ktile;
-      gp.K = L.Kp - (a->img_C - a->img_kept_C); gp.lda = L.Kp; gp.ldw = L.Kp;
+    if (plan.rowvec != ROWVEC_NONE) {
+      // the perceptual block (percep_proj: the first img_C columns) or its projected levels' columns (img_proj: img_kept_C ..
+      // img_C, the K-tile gap) are left out of the K loop; their contribution was sampled from the projected map / channels
+      // into the row vector and is added in the epilogue
+      if (plan.rowvec == ROWVEC_X_HEAD) {
+        const int64_t skip = (int64_t)a->img_C * (gp.x3i ? 4 : 2);
+        gp.a_hi += skip; gp.w_hi += skip;
+      } else if (a->H1 * 4 > L.Kp * 2) {
+        return fail(LIST_ERR_UNSUPPORTED, "img_proj: H1 * 4 bytes exceed a row of the feature matrix's lo plane");
+      }
+      gp.k_gap_at = plan.k_gap_at; gp.k_gap = plan.k_gap; gp.lda = L.Kp; gp.ldw = L.Kp;
       gp.rowvec = (const char*)g.rowvec; gp.rowvec_stride = g.rv_stride * 4;
-      if (a->H1 * 4 > L.Kp * 2) return fail(LIST_ERR_UNSUPPORTED, "img_proj: H1 * 4 bytes exceed a row of the feature matrix's lo plane");
     }
     const char* rowvec_of_call = gp.rowvec;
     gp.out_hi = (unsigned short*)(wsb + ws.h1_hi);
@@ -688,16 +636,16 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     // of those tiles are redone with the reference's skip semantics and fc_0 runs again for them.  On finite
     // inputs both gated launches exit at their first instruction.
     gp.nan_tiles = nan_tiles;
-    if (fused0) {
+    if (plan.fc0 == FC0_FUSED) {
       // the perceptual block of X is produced inside fc_0 (fused_fc0_kernels.hip): no 2-D gather launch above, those
       // columns of X stay unwritten (the exact redo below rewrites them for the tiles it flags)
       FusedFc0Params fp;
       fp.gp = gp; fp.g = g; fp.img_map = a->img_map; fp.trans_mat = a->trans_mat;
-      fp.ms = a->map_size; fp.Ct = a->img_C; fp.clamp_hi = a->clamp_hi; fp.n_produced = fused_produced_tiles(a);
+      fp.ms = a->map_size; fp.Ct = a->img_C; fp.clamp_hi = a->clamp_hi; fp.n_produced = plan.n_produced;
       if (!fused_fc0_eligible(fp.gp, a->img_dtype == LIST_MAP_F16, a->img_C))
         return fail(LIST_ERR_ARG, "internal: fused fc_0 taken for arguments it does not support");
       e = launch_fc0_fused(fp, terms, s);
-    } else if (sampled0) {
+    } else if (plan.fc0 == FC0_SAMPLED) {
       // the kept levels' K-tiles come from X like every other tile; the epilogue samples the projected channels from
       // the map (no row-vector buffer).  The exact redo below takes the row vectors the fix-up kernel writes for the
       // tiles it flags.
@@ -727,7 +675,7 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     gp.out_hi = (unsigned short*)(wsb + ws.h2_hi);
     gp.out_lo = terms == 3 ? (unsigned short*)(wsb + ws.h2_lo) : nullptr;
     gp.ldo = a->H2;
-    if (takes_fused_tail(a)) {
+    if (plan.fused_tail) {
       // inference: fc_1, fc_2 and fc_out in one kernel, H2 stays in registers (gemm_kernels.hip, k_mlp_tail_f16)
       mark(LIST_STAGE_FC1);
       e = launch_mlp_tail(gp, wp + pk.w2_hi, (const float*)(wp + pk.b2), (const float*)(wp + pk.w3),
@@ -744,11 +692,8 @@ int list_sdf_query_fwd(const ListQueryArgs* a, void* stream) {
     gp.w_hi = wp + pk.w2_hi; gp.w_lo = wp + pk.w2_lo;
     gp.bias = (const float*)(wp + pk.b2);
     gp.N = a->H3; gp.K = a->H2;
-    // H3 is kept with H1 / H2 for list_sdf_query_bwd (its head needs relu(fc_2): mask, dZ3, d fc_out.weight) -- by
-    // forwards a backward can follow only: an inference forward that misses the fused tail above (bf16 formats, the
-    // 256^3 grid of config 4 among them) would write 1 KB per point that nobody reads
-    gp.out_hi = a->no_activations ? nullptr : (unsigned short*)(wsb + ws.h3_hi);
-    gp.out_lo = (terms == 3 && !a->no_activations) ? (unsigned short*)(wsb + ws.h3_lo) : nullptr;
+    gp.out_hi = plan.keep_h3 ? (unsigned short*)(wsb + ws.h3_hi) : nullptr;       // (for list_sdf_query_bwd's head)
+    gp.out_lo = (terms == 3 && plan.keep_h3) ? (unsigned short*)(wsb + ws.h3_lo) : nullptr;
     gp.ldo = a->H3;
     gp.w3 = (const float*)(wp + pk.w3); gp.b3 = (const float*)(wp + pk.b3);
     gp.sdf = a->sdf + p0; gp.n_valid = n_valid; gp.order = g.order;
@@ -766,6 +711,7 @@ int list_query_plan(const ListQueryArgs* a, ListQueryPlan* plan) {
   if (a && a->B >= 0 && a->N >= 0 && (int64_t)a->B * a->N == 0) return LIST_OK;   // empty query: no launch at all
   int rc = check_query_common(a, &L);
   if (rc != LIST_OK) return rc;
+  // (no launch: positive sizes are all the plan needs; the call itself holds them to check_hidden)
   if (a->H1 <= 0 || a->H2 <= 0) return fail(LIST_ERR_UNSUPPORTED, "hidden sizes %d/%d/%d", a->H1, a->H2, a->H3);
   const int64_t P = (int64_t)a->B * a->N;
   const int64_t rows = chunk_rows_for(a->workspace_bytes, P, L.Kp, a->H1, a->H2);
@@ -773,16 +719,12 @@ int list_query_plan(const ListQueryArgs* a, ListQueryPlan* plan) {
                                    a->workspace_bytes, kRowTile);
   plan->rows_per_chunk = rows;
   plan->chunks = (int32_t)((P + rows - 1) / rows);
-  plan->fused_tail = takes_fused_tail(a) ? 1 : 0;
-  plan->fc0_k = a->percep_proj ? L.Kp - a->img_C : a->img_proj ? L.Kp - (a->img_C - a->img_kept_C) : L.Kp;
-  plan->img_proj = a->img_proj ? 1 : 0;
-  {
-    const Workspace ws = workspace_layout(rows, L.Kp, a->H1, a->H2);
-    const int n_valid = (int)(P < rows ? P : rows);
-    const GatherParams g = make_gather(a, L, ws, 0, n_valid, (n_valid + kRowTile - 1) / kRowTile * kRowTile);
-    plan->box_levels = gather_box_levels(g, L, *a);
-    plan->fused_fc0 = fc0_samples_map(a, L) ? 1 : 0;
-  }
+  const QueryFwdPlan p = plan_for(a, L, rows, false);
+  plan->fused_tail = p.fused_tail ? 1 : 0;
+  plan->fc0_k = p.fc0_k;
+  plan->img_proj = p.k_gap != 0 ? 1 : 0;
+  plan->box_levels = p.box_levels;
+  plan->fused_fc0 = (p.img == IMG_NONE || p.fc0 == FC0_SAMPLED) ? 1 : 0;       // fc_0 samples the map itself
   return LIST_OK;
 }
 
@@ -798,12 +740,13 @@ int list_gather_features_fwd(const ListQueryArgs* a, float* out, void* stream) {
   if (rows < kRowTile) return fail(LIST_ERR_WORKSPACE, "workspace too small");
   const Workspace ws = workspace_layout(rows, L.Kp, H1, H2);
   hipStream_t s = (hipStream_t)stream;
+  const QueryFwdPlan plan = plan_for(a, L, rows, /*gather_only=*/true);
   for (int64_t p0 = 0; p0 < P; p0 += rows) {
     const int n_valid = (int)((P - p0 < rows) ? (P - p0) : rows);
     const int crow = (n_valid + kRowTile - 1) / kRowTile * kRowTile;
     GatherParams g = make_gather(a, L, ws, p0, n_valid, crow);
     int* nan_tiles = (int*)((char*)a->workspace + ws.nan_tiles);
-    hipError_t e = launch_gather(g, L, *a, nan_tiles, s);
+    hipError_t e = launch_gather(g, L, *a, plan, nan_tiles, s);
     if (e != hipSuccess) return hip_fail(e, "gather launch");
     e = launch_features_out(g, L, out, nan_tiles, s);
     if (e != hipSuccess) return hip_fail(e, "features_out launch");
@@ -869,12 +812,8 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   if (ga->grad_img_levels) {
     if (!ga->grad_img_map) return fail(LIST_ERR_ARG, "grad_img_levels needs grad_img_map as its intermediate");
     if (a->map_size > 320) return fail(LIST_ERR_SHAPE, "grad_img_levels: map_size=%d (need <= 320)", a->map_size);
-    int ct = 0;
-    for (int i = 0; i < LIST_N_IMG_LEVELS; ++i) {
-      const ListMap2D& m = ga->grad_img_levels[i];
-      if (m.C < 1 || m.H < 1 || m.W < 1) return fail(LIST_ERR_SHAPE, "grad_img_levels[%d]: bad descriptor", i);
-      ct += m.C;
-    }
+    int ct;
+    if ((rc = check_img_levels(ga->grad_img_levels, false, "grad_img_levels", &ct))) return rc;
     if (ct != a->img_C) return fail(LIST_ERR_SHAPE, "grad_img_levels: channels sum to %d, the map has %d", ct, a->img_C);
   }
   if (ga->grad_img_map_dtype != LIST_MAP_F32 && ga->grad_img_map_dtype != LIST_MAP_F16)
@@ -885,7 +824,7 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
       return fail(LIST_ERR_ARG, "grad_img_map_dtype = F16 is the intermediate of grad_img_levels: pass both");
     if (a->precision != LIST_PREC_FP16)
       return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs fp16 operands (fwd->precision FP16)");
-    if (a->no_sort || a->percep_feat || a->B > kSortImages || a->map_size * ((a->map_size + 3) / 4) > kSortPixCells)
+    if (a->B > kSortImages || !sort_has_pixel_order(*a))
       return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs the pixel-ordered gather form (point sort on, "
                                         "B <= %d, map_size * ceil(map_size / 4) <= %d)", kSortImages, kSortPixCells);
     if (a->img_C % 4) return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs img_C %% 4 == 0");
@@ -897,12 +836,10 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   if (!ga->grad_sdf || !ga->packed_mlp_bwd || !a->packed_mlp || !ga->workspace)
     return fail(LIST_ERR_ARG, "grad_sdf/packed_mlp_bwd/packed_mlp/workspace is NULL");
   if (a->F != L.F) return fail(LIST_ERR_SHAPE, "F=%d but channels give %d", a->F, L.F);
-  if (a->H1 % 256 || a->H2 % 256 || a->H3 != 256 || a->H1 <= 0 || a->H2 <= 0)
-    return fail(LIST_ERR_UNSUPPORTED, "hidden sizes %d/%d/%d", a->H1, a->H2, a->H3);
+  if ((rc = check_hidden(a->H1, a->H2, a->H3))) return rc;
   if (a->H1 > 2048 || a->H2 > 2048)
     return fail(LIST_ERR_UNSUPPORTED, "backward supports hidden sizes up to 2048 (got %d/%d)", a->H1, a->H2);
-  if (a->precision < LIST_PREC_BF16X3 || a->precision > LIST_PREC_FP16)
-    return fail(LIST_ERR_ARG, "precision=%d", a->precision);
+  if ((rc = check_precision(a->precision))) return rc;
   if (ga->vox_adjoint < 0 || ga->vox_adjoint > 2) return fail(LIST_ERR_ARG, "vox_adjoint=%d", ga->vox_adjoint);
   if (a->percep_proj) return fail(LIST_ERR_UNSUPPORTED, "a forward with percep_proj (inference) keeps no perceptual features for the backward");
   if (a->img_proj) return fail(LIST_ERR_UNSUPPORTED, "a forward with img_proj (inference) keeps no perceptual features for the backward");
@@ -1001,7 +938,7 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   ScatterParams sp;
   sp.g = make_gather(a, L, ws, 0, n_valid, crow);
   sp.g.order = order;
-  const bool pix = !a->no_sort && !a->percep_feat && a->map_size * ((a->map_size + 3) / 4) <= kSortPixCells;
+  const bool pix = sort_has_pixel_order(*a);
   if (pix) { sp.g.order_img = (const int*)(fw + ws.order_img); sp.g.row_of = (const int*)(fw + ws.row_of); }
   sp.dx = bwp + bw.dx; sp.dx_f16 = fp16 ? 1 : 0; sp.scale = scale; sp.forked = forked ? 1 : 0;
   VoxGatherBuffers vb;
@@ -1223,12 +1160,8 @@ int list_img_map_grad_to_levels(const float* grad_img_map, int32_t B, int32_t ma
   if (!grad_img_map || !grads) return fail(LIST_ERR_ARG, "NULL pointer");
   if (B <= 0 || map_size < 2 || map_size > 320)
     return fail(LIST_ERR_SHAPE, "B=%d map_size=%d (need 2..320)", B, map_size);
-  int Ct = 0;
-  for (int i = 0; i < LIST_N_IMG_LEVELS; ++i) {
-    if (grads[i].C < 1 || grads[i].H < 1 || grads[i].W < 1)
-      return fail(LIST_ERR_SHAPE, "image level %d: bad descriptor", i);
-    Ct += grads[i].C;
-  }
+  int Ct;
+  if (int rc = check_img_levels(grads, false, "image level", &Ct)) return rc;
   hipError_t e = launch_img_grad_to_levels(grad_img_map, B, map_size, Ct, grads, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "img_grad_to_levels launch");
   return LIST_OK;
@@ -1238,7 +1171,7 @@ int list_gemm_tn(const void* a_hi, const void* a_lo, const void* b_hi, const voi
                  void* slab, size_t slab_bytes, int32_t M, int32_t N, int32_t P, int32_t precision,
                  void* stream) {
   if (!a_hi || !b_hi || !out || !slab) return fail(LIST_ERR_ARG, "NULL pointer");
-  if (precision < LIST_PREC_BF16X3 || precision > LIST_PREC_FP16) return fail(LIST_ERR_ARG, "precision=%d", precision);
+  if (int rc = check_precision(precision)) return rc;
   if (precision == LIST_PREC_BF16X3 && (!a_lo || !b_lo)) return fail(LIST_ERR_ARG, "lo planes missing");
   if (M <= 0 || M % 256 || N < 8 || N % 8 || P <= 0 || P % 256)
     return fail(LIST_ERR_SHAPE, "M=%d N=%d P=%d (need M,P %% 256 == 0, N %% 8 == 0)", M, N, P);
@@ -1269,7 +1202,7 @@ int list_gemm_nt(const void* a_hi, const void* a_lo, const void* w_hi, const voi
                  int32_t precision, void* stream) {
   if (!a_hi || !w_hi || !out) return fail(LIST_ERR_ARG, "NULL pointer");
   if (precision == LIST_PREC_BF16X3 && (!a_lo || !w_lo)) return fail(LIST_ERR_ARG, "lo planes missing");
-  if (precision < LIST_PREC_BF16X3 || precision > LIST_PREC_FP16) return fail(LIST_ERR_ARG, "precision=%d", precision);
+  if (int rc = check_precision(precision)) return rc;
   if (M <= 0 || M % 256 || N <= 0 || N % 256 || K <= 0 || K % 64)
     return fail(LIST_ERR_SHAPE, "M=%d N=%d K=%d (need M,N %% 256 == 0, K %% 64 == 0)", M, N, K);
   if (!aligned16(a_hi) || !aligned16(w_hi) || (a_lo && !aligned16(a_lo)) || (w_lo && !aligned16(w_lo)))

@@ -9,6 +9,7 @@
 
 #include "list_hip.h"
 #include "vox_adjoint_plan.h"       // kDisp (the stencil displacement) and what chooses a voxel level's adjoint form
+#include "query_fwd_plan.h"         // what chooses the forward's launches; kSortPixCells, kBoxPts
 
 namespace list {
 
@@ -263,7 +264,7 @@ inline PackedMlpBwd packed_mlp_bwd_layout(int Kp, int H1, int H2, int H3) {
 }
 
 // ---- backward workspace -----------------------------------------------------------------------------------
-constexpr int kSortImagesC = 64, kSortPixCellsC = 8192;      // (= kSortImages, kSortPixCells below; needed above them)
+constexpr int kSortImages = 64;          // image slots in the point sort's key (b % 64)
 constexpr int kColsumRows = 256;         // rows per partial of the bias-gradient column sums
 constexpr int kWgradMaxSplits = 128;
 
@@ -272,7 +273,7 @@ constexpr int kWgradMaxSplits = 128;
 // number at most 4 rows / 1024 whole ones plus one partial chunk per heavy group (<= 4 rows / 1024 of those).
 inline int img_heavy_max_chunks(int64_t rows) { return (int)(8 * rows / 1024 + 8); }
 inline size_t img_heavy_bytes(int64_t rows, int Ct) {
-  return 256 + (size_t)kSortImagesC * kSortPixCellsC * 4 + (size_t)img_heavy_max_chunks(rows) * 8 + 256 +
+  return 256 + (size_t)kSortImages * kSortPixCells * 4 + (size_t)img_heavy_max_chunks(rows) * 8 + 256 +
          (size_t)img_heavy_max_chunks(rows) * 4 * Ct * 4;
 }
 
@@ -291,6 +292,11 @@ inline int wgrad_nominal_splits(int M, int N) {     // enough workgroups to fill
   const int tiles = (M / 256) * ((N + 255) / 256);
   int s = 512 / (tiles > 0 ? tiles : 1);
   return s > kWgradMaxSplits ? kWgradMaxSplits : (s < 1 ? 1 : s);
+}
+inline int wgrad_splits(int M, int N, int P, int terms) {     // ... capped at the K-steps there are
+  const int nk = P / (terms == 3 ? 32 : 64);
+  const int s = wgrad_nominal_splits(M, N);
+  return s > nk ? (nk < 1 ? 1 : nk) : s;
 }
 inline size_t wgrad_slab_bytes(int Kp, int H1, int H2, int H3) {
   size_t big = (size_t)H1 * Kp * wgrad_nominal_splits(H1, Kp);
@@ -326,8 +332,6 @@ inline BwdWorkspace bwd_workspace_layout(int64_t rows, int Kp, int H1, int H2, i
 // ---- per-chunk workspace --------------------------------------------------------------------
 constexpr int kSortCellsPerAxis = 16;                        // Morton cells per axis per image
 constexpr int kSortCells = kSortCellsPerAxis * kSortCellsPerAxis * kSortCellsPerAxis;   // 4096
-constexpr int kSortImages = kSortImagesC;                    // image slots in the key (b % 64)
-constexpr int kSortPixCells = kSortPixCellsC;                // pixel-order bins per image (>= ms * ceil(ms/4))
 constexpr int kSortBins = (kSortCells + kSortPixCells) * kSortImages;   // Morton + pixel counters (3 MB)
 
 constexpr int kH3 = 256;                             // fc_2's width: the C API accepts no other (list_capi.hip)
@@ -466,20 +470,16 @@ hipError_t launch_split_xi(const float* x, unsigned short* out, int64_t n, hipSt
 hipError_t launch_split(const float* x, unsigned short* hi, unsigned short* lo, int64_t n, int fmt,
                         hipStream_t s, int order = 0);
 struct SortBuffers { int* order; int* order_img; int* row_of; int* keys; int* keys2; int* bins; };
-hipError_t launch_sort_points(const GatherParams& g, const ListQueryArgs& a, const SortBuffers& sb,
-                              hipStream_t s);
+hipError_t launch_sort_points(const GatherParams& g, const ListQueryArgs& a, const SortBuffers& sb, bool pixel,
+                              hipStream_t s);       // pixel: the pixel order too (QueryFwdPlan.sort)
+// the voxel levels, the 2-D gather and the tail as `plan` has them (query_fwd_plan.h)
 // nan_tiles: int32 [rows / 256], cleared by the last gather kernel (the flags of fc_0's NaN probe)
-// skip_img: the 2-D gather is left out (its columns of X are produced inside the fused fc_0, fused_fc0_kernels.hip)
-// img_proj without g.rowvec: the 2-D gather samples the kept channels only, in the order of the rows (fc_0's epilogue
-// samples the projected ones, EPI_RELU_SAMPLE)
-hipError_t launch_gather(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a,
-                         int* nan_tiles, hipStream_t s, bool skip_img = false);
+hipError_t launch_gather(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a, const QueryFwdPlan& plan,
+                         int* nan_tiles, hipStream_t s);
 hipError_t launch_features_out(const GatherParams& g, const FeatLayout& L, float* out, int* nan_tiles,
                                hipStream_t s);
-// coarse levels on the matrix cores (gather_box_kernels.hip); eligible: near level, C = 128, fp16 maps and fp16 X
-bool gather_box_eligible(const GatherParams& g, const ListVoxLevel& lv, int col_off);
+// coarse levels on the matrix cores (gather_box_kernels.hip; gather_box_eligible: query_fwd_plan.h)
 hipError_t launch_gather_vox_box(const GatherParams& g, const ListVoxLevel& lv, int col_off, hipStream_t s, int order);
-int gather_box_levels(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a);     // bitmask of such levels
 // exact (reference skip semantics) redo of the voxel and 2-D gathers for the 256-row tiles flagged in tile_flags
 hipError_t launch_gather_fixup(const GatherParams& g, const FeatLayout& L, const ListQueryArgs& a,
                                const int* tile_flags, hipStream_t s);
@@ -506,7 +506,6 @@ hipError_t launch_mlp_tail(const GemmParams& fc1, const char* w2, const float* b
 hipError_t launch_prep_weights_bwd(const ListMlpWeights& w, const FeatLayout& L, const PackedMlpBwd& P,
                                    char* packed, hipStream_t s);
 hipError_t launch_gemm_tn(const GemmTnParams& p, int terms, hipStream_t s);
-int wgrad_splits(int M, int N, int P, int terms);
 // out[m][col(n)] = inv_scale * sum_s slab[s][m][n]; L != nullptr: n is a gather-order column of fc_0,
 // written to its reference column (padding dropped); ldo = row stride of out
 hipError_t launch_wgrad_reduce(const float* slab, int splits, int M, int N, int ldn, const FeatLayout* L,
