@@ -837,6 +837,14 @@ __global__ __launch_bounds__(256) void k_img_records(GatherParams g, const float
   ImgRec r;
   r.x0 = pr.x0; r.y0 = pr.y0; r.row = row; r.b = p.b;
   r.wx0 = pr.wx0; r.wx1 = pr.wx1; r.wy0 = pr.wy0; r.wy1 = pr.wy1;
+  // zeros padding, as in the forward (Proj::dead, point_math.h): under a clamp beyond the map (network/modules.py:43 with
+  // map_size < 137) a tap outside the map gives no value, so it takes no gradient -- x0 / y0 are clamped INTO the map, and
+  // their weights would otherwise land on its last column / row.  (A NaN weight stays NaN, as there.)
+  const float fx = floorf(pr.ix), fy = floorf(pr.iy), last = (float)(ms - 1);
+  if (!(fx >= 0.f && fx <= last) && r.wx0 == r.wx0) r.wx0 = 0.f;
+  if (!(fx + 1.f <= last) && r.wx1 == r.wx1) r.wx1 = 0.f;
+  if (!(fy >= 0.f && fy <= last) && r.wy0 == r.wy0) r.wy0 = 0.f;
+  if (!(fy + 1.f <= last) && r.wy1 == r.wy1) r.wy1 = 0.f;
   recs[slot] = r;
 }
 

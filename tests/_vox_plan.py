@@ -19,7 +19,7 @@ def build_host(directory):
 
 def case(B, N, R=128, fp16=True, forked=True, mode=0, gather_buffers=True, box_mode=-1, f32=False, shift=0, edits=()):
     """One call of the rule.  mode: ListQueryGradArgs.vox_adjoint; box_mode, f32: LIST_SCATTER_BOX (-1: unset) and
-    LIST_SCATTER_F32; shift: added to every level's column offset; edits: "lK.null", "lK.C=V", "lK.stride+V"."""
+    LIST_SCATTER_F32; shift: added to every level's column offset; edits: "lK.null", "lK.C=V", "lK.stride+V", "lK.dims=D,H,W", "lK.off=V"."""
     return [B, N, R, int(fp16), int(forked), mode, int(gather_buffers), box_mode, int(f32), shift, *edits]
 
 

@@ -3,7 +3,8 @@
 //   name B N R fp16 forked mode gather_buffers box_mode f32_diagnostic offset_shift [edit ...]
 // The pyramid is C = 1, 16, 32, 64, 128, 128 at R^3, R^3, (R/2)^3 .. (R/16)^3, dense, 16-byte-aligned, non-null, at the
 // column offsets of make_layout for img_C = 1024 (plus offset_shift), Kp = 3648; rows = B * N rounded up to 256, the
-// scratch rows x 512 and rows x 256 halfs when fp16.  Edits change one level first: lK.null, lK.C=V, lK.stride+V.
+// scratch rows x 512 and rows x 256 halfs when fp16.  Edits change one level first: lK.null, lK.C=V, lK.stride+V,
+// lK.dims=D,H,W (the level's size, dense) and lK.off=V (its column offset, the shift included).
 // Output: one line "name l form/lane/flush" per level.
 #include <stdio.h>
 #include <stdlib.h>
@@ -50,8 +51,13 @@ int main() {
       col_off[l] = kOff[l] + (int)v[9];
     }
     while ((tok = strtok(nullptr, " \n"))) {
-      int l = -1, val = 0;
-      if (sscanf(tok, "l%d.C=%d", &l, &val) == 2 && l >= 0 && l < LIST_N_VOX_LEVELS) {
+      int l = -1, val = 0, d = 0, h = 0, w = 0;
+      if (sscanf(tok, "l%d.dims=%d,%d,%d", &l, &d, &h, &w) == 4 && l >= 0 && l < LIST_N_VOX_LEVELS && d > 0 && h > 0 && w > 0) {
+        lv[l].D = d; lv[l].H = h; lv[l].W = w;
+        lv[l].image_stride = (int64_t)d * h * w * lv[l].C;
+      } else if (sscanf(tok, "l%d.off=%d", &l, &val) == 2 && l >= 0 && l < LIST_N_VOX_LEVELS) {
+        col_off[l] = val;
+      } else if (sscanf(tok, "l%d.C=%d", &l, &val) == 2 && l >= 0 && l < LIST_N_VOX_LEVELS) {
         lv[l].C = val;
         lv[l].image_stride = (int64_t)lv[l].D * lv[l].H * lv[l].W * val;
       } else if (sscanf(tok, "l%d.stride+%d", &l, &val) == 2 && l >= 0 && l < LIST_N_VOX_LEVELS) {
