@@ -15,12 +15,12 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "liblist_hip.so")
 SOURCES = ["prep_kernels.hip", "gather_kernels.hip", "gather_box_kernels.hip", "gemm_kernels.hip", "fused_fc0_kernels.hip", "bwd_mlp_kernels.hip",
-           "bwd_scatter_kernels.hip", "bwd_box_kernels.hip", "list_capi.hip",
+           "bwd_scatter_kernels.hip", "bwd_img_kernels.hip", "bwd_box_kernels.hip", "list_capi.hip",
            "mesh_kernels.hip", "eval_kernels.hip", "data_kernels.hip", "loss_kernels.hip",
            "refine_kernels.hip", "voxenc_kernels.hip", "coarse_kernels.hip", "imgenc_kernels.hip", "s2loss_kernels.hip",
            "augment_kernels.hip", "resize_kernels.hip", "components_kernels.hip", "render_kernels.hip", "simplify_kernels.hip",
            "objtext_kernels.hip"]
-HEADERS = ["list_common.h", "vox_adjoint_plan.h", "query_fwd_plan.h", "list_host.h", "list_cub.h", "point_math.h", "gather_math.h", "mfma_common.h", "box_partition.h", "mc_tables.h",
+HEADERS = ["list_common.h", "vox_adjoint_plan.h", "query_fwd_plan.h", "query_bwd_plan.h", "list_host.h", "list_cub.h", "point_math.h", "gather_math.h", "mfma_common.h", "box_partition.h", "mc_tables.h",
            "stage_prep.h", "s2loss_math.h", "augment_math.h", "augment_check.h", "resize_math.h", "render_math.h", "simplify_math.h",
            "objtext_math.h", "objtext_tables.h"]
 PUBLIC_HEADERS = ["list_hip.h", "list_mesh.h", "list_eval.h", "list_data.h", "list_loss.h", "list_refine.h", "list_voxenc.h",

@@ -191,6 +191,103 @@ QueryFwdPlan plan_for(const ListQueryArgs* a, const FeatLayout& L, int64_t rows,
   return plan_query_fwd({a, L.Kp, L.img_off, (int)rows, L.vox_off, sw.fused_fc0, sw.gather_box, sw.tail_ride, gather_only});
 }
 
+// list_sdf_query_bwd's arguments (behind the NULL and the empty-query checks); *rows_out: the rows of the call's one chunk
+int check_query_bwd(const ListQueryGradArgs* ga, FeatLayout* L, int64_t* rows_out) {
+  const ListQueryArgs* a = ga->fwd;
+  int rc = check_query_common(a, L);
+  if (rc != LIST_OK) return rc;
+  if (ga->grad_img_levels) {
+    if (!ga->grad_img_map) return fail(LIST_ERR_ARG, "grad_img_levels needs grad_img_map as its intermediate");
+    if (a->map_size > 320) return fail(LIST_ERR_SHAPE, "grad_img_levels: map_size=%d (need <= 320)", a->map_size);
+    int ct;
+    if ((rc = check_img_levels(ga->grad_img_levels, false, "grad_img_levels", &ct))) return rc;
+    if (ct != a->img_C) return fail(LIST_ERR_SHAPE, "grad_img_levels: channels sum to %d, the map has %d", ct, a->img_C);
+  }
+  if (ga->grad_img_map_dtype != LIST_MAP_F32 && ga->grad_img_map_dtype != LIST_MAP_F16)
+    return fail(LIST_ERR_ARG, "grad_img_map_dtype=%d", ga->grad_img_map_dtype);
+  if (ga->grad_img_map_dtype == LIST_MAP_F16) {
+    // halfs at the gradient scale between the map-side gather and the adjoint resize: an intermediate, not an output
+    if (!ga->grad_img_levels || !ga->grad_img_map)
+      return fail(LIST_ERR_ARG, "grad_img_map_dtype = F16 is the intermediate of grad_img_levels: pass both");
+    if (a->precision != LIST_PREC_FP16)
+      return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs fp16 operands (fwd->precision FP16)");
+    if (!map_grad_gathers(*a))
+      return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs the pixel-ordered gather form (point sort on, "
+                                        "B <= %d, map_size * ceil(map_size / 4) <= %d)", kSortImages, kSortPixCells);
+    if (a->img_C % 4) return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs img_C %% 4 == 0");
+  }
+  if (a->percep_feat && (ga->grad_img_map || ga->grad_trans_mat))
+    return fail(LIST_ERR_ARG, "with percep_feat the perceptual gradient is grad_percep_feat, not grad_img_map/grad_trans_mat");
+  if (!a->percep_feat && ga->grad_percep_feat)
+    return fail(LIST_ERR_ARG, "grad_percep_feat needs the pre-pooled form (fwd->percep_feat)");
+  if (!ga->grad_sdf || !ga->packed_mlp_bwd || !a->packed_mlp || !ga->workspace)
+    return fail(LIST_ERR_ARG, "grad_sdf/packed_mlp_bwd/packed_mlp/workspace is NULL");
+  if (a->F != L->F) return fail(LIST_ERR_SHAPE, "F=%d but channels give %d", a->F, L->F);
+  if ((rc = check_hidden(a->H1, a->H2, a->H3))) return rc;
+  if (a->H1 > 2048 || a->H2 > 2048)
+    return fail(LIST_ERR_UNSUPPORTED, "backward supports hidden sizes up to 2048 (got %d/%d)", a->H1, a->H2);
+  if ((rc = check_precision(a->precision))) return rc;
+  if (ga->vox_adjoint < 0 || ga->vox_adjoint > 2) return fail(LIST_ERR_ARG, "vox_adjoint=%d", ga->vox_adjoint);
+  if (a->percep_proj) return fail(LIST_ERR_UNSUPPORTED, "a forward with percep_proj (inference) keeps no perceptual features for the backward");
+  if (a->img_proj) return fail(LIST_ERR_UNSUPPORTED, "a forward with img_proj (inference) keeps no perceptual features for the backward");
+  if (a->no_activations) return fail(LIST_ERR_ARG, "a forward with no_activations = 1 (inference) keeps no H1 / H2 for the backward");
+  const int64_t P = (int64_t)a->B * a->N;
+  if (P > kMaxChunkRows)
+    return fail(LIST_ERR_UNSUPPORTED, "backward handles up to %lld points per call (got %lld)",
+                (long long)kMaxChunkRows, (long long)P);
+  const int64_t rows = *rows_out = chunk_rows_for(a->workspace_bytes, P, L->Kp, a->H1, a->H2);
+  if (rows < P)
+    return fail(LIST_ERR_WORKSPACE, "forward workspace does not hold the whole query in one chunk");
+  const BwdWorkspace bw = bwd_workspace_layout(rows, L->Kp, a->H1, a->H2, a->H3, a->precision == LIST_PREC_FP16);
+  if (ga->workspace_bytes < bw.total)
+    return fail(LIST_ERR_WORKSPACE, "backward workspace too small: %zu < %zu", ga->workspace_bytes, bw.total);
+  if (!aligned16(ga->workspace)) return fail(LIST_ERR_SHAPE, "workspace must be 16-byte aligned");
+  for (int l = 0; l < LIST_N_VOX_LEVELS; ++l) {
+    const ListVoxLevel& gv = ga->grad_vox[l];
+    if (!gv.data) continue;
+    const ListVoxLevel& v = a->vox[l];
+    if (gv.C != v.C || gv.D != v.D || gv.H != v.H || gv.W != v.W || gv.dtype != LIST_MAP_F32 ||
+        gv.image_stride != (int64_t)v.C * v.D * v.H * v.W)
+      return fail(LIST_ERR_SHAPE, "grad_vox[%d] must be fp32 [B][D][H][W][C] of the level's shape", l);
+  }
+  return LIST_OK;
+}
+
+// `to` continues after `from`'s work so far
+hipError_t hand_over(hipStream_t from, hipStream_t to) {
+  if (from == to) return hipSuccess;
+  hipEvent_t ev;
+  hipError_t err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (err != hipSuccess) return err;
+  err = hipEventRecord(ev, from);
+  if (err == hipSuccess) err = hipStreamWaitEvent(to, ev, 0);
+  (void)hipEventDestroy(ev);                    // released once the wait has been satisfied
+  return err;
+}
+// the main lane continues after every other lane's work so far (all of them are tried; the first error is returned)
+hipError_t join_all(const hipStream_t (&lane)[4]) {
+  hipError_t first = hipSuccess;
+  for (int l = 1; l < 4; ++l) {
+    const hipError_t err = hand_over(lane[l], lane[kLaneMain]);
+    if (first == hipSuccess) first = err;
+  }
+  return first;
+}
+
+// LIST_BWD_TRANS_UNORDERED, read once (QueryBwdCall has its value), and the call's plan
+QueryBwdPlan plan_bwd_for(const ListQueryGradArgs* ga, const FeatLayout& L, int64_t rows, size_t heavy_bytes) {
+  static const bool unordered = [] { const char* e = getenv("LIST_BWD_TRANS_UNORDERED"); return e && e[0] == '1'; }();
+  const ListMlpGrads& m = ga->mlp;
+  bool vox = false;
+  for (int l = 0; l < LIST_N_VOX_LEVELS; ++l) vox = vox || ga->grad_vox[l].data;
+  const int n_aux = ga->aux_streams[0] && ga->aux_streams[1] ? (ga->aux_streams[2] ? 3 : 2) : 0;
+  return plan_query_bwd({ga->fwd, {m.w0 != nullptr, m.b0 != nullptr, m.w1 != nullptr, m.b1 != nullptr, m.w2 != nullptr,
+                                   m.b2 != nullptr, m.w3 != nullptr, m.b3 != nullptr},
+                         ga->grad_img_map != nullptr, ga->grad_img_map_dtype == LIST_MAP_F16, ga->grad_img_levels != nullptr,
+                         ga->grad_trans_mat != nullptr, ga->grad_percep_feat != nullptr, vox, n_aux, rows, L.img_C, heavy_bytes,
+                         unordered, false});
+}
+
 }  // namespace
 
 extern "C" {
@@ -805,66 +902,14 @@ size_t list_query_bwd_workspace_bytes(int64_t n_points, int32_t F, int32_t H1, i
 int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   if (!ga || !ga->fwd) return fail(LIST_ERR_ARG, "args/fwd is NULL");
   const ListQueryArgs* a = ga->fwd;
-  FeatLayout L;
   if (a->B >= 0 && a->N >= 0 && (int64_t)a->B * a->N == 0) return LIST_OK;
-  int rc = check_query_common(a, &L);
-  if (rc != LIST_OK) return rc;
-  if (ga->grad_img_levels) {
-    if (!ga->grad_img_map) return fail(LIST_ERR_ARG, "grad_img_levels needs grad_img_map as its intermediate");
-    if (a->map_size > 320) return fail(LIST_ERR_SHAPE, "grad_img_levels: map_size=%d (need <= 320)", a->map_size);
-    int ct;
-    if ((rc = check_img_levels(ga->grad_img_levels, false, "grad_img_levels", &ct))) return rc;
-    if (ct != a->img_C) return fail(LIST_ERR_SHAPE, "grad_img_levels: channels sum to %d, the map has %d", ct, a->img_C);
-  }
-  if (ga->grad_img_map_dtype != LIST_MAP_F32 && ga->grad_img_map_dtype != LIST_MAP_F16)
-    return fail(LIST_ERR_ARG, "grad_img_map_dtype=%d", ga->grad_img_map_dtype);
-  if (ga->grad_img_map_dtype == LIST_MAP_F16) {
-    // halfs at the gradient scale between the map-side gather and the adjoint resize: an intermediate, not an output
-    if (!ga->grad_img_levels || !ga->grad_img_map)
-      return fail(LIST_ERR_ARG, "grad_img_map_dtype = F16 is the intermediate of grad_img_levels: pass both");
-    if (a->precision != LIST_PREC_FP16)
-      return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs fp16 operands (fwd->precision FP16)");
-    if (a->B > kSortImages || !sort_has_pixel_order(*a))
-      return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs the pixel-ordered gather form (point sort on, "
-                                        "B <= %d, map_size * ceil(map_size / 4) <= %d)", kSortImages, kSortPixCells);
-    if (a->img_C % 4) return fail(LIST_ERR_UNSUPPORTED, "grad_img_map_dtype = F16 needs img_C %% 4 == 0");
-  }
-  if (a->percep_feat && (ga->grad_img_map || ga->grad_trans_mat))
-    return fail(LIST_ERR_ARG, "with percep_feat the perceptual gradient is grad_percep_feat, not grad_img_map/grad_trans_mat");
-  if (!a->percep_feat && ga->grad_percep_feat)
-    return fail(LIST_ERR_ARG, "grad_percep_feat needs the pre-pooled form (fwd->percep_feat)");
-  if (!ga->grad_sdf || !ga->packed_mlp_bwd || !a->packed_mlp || !ga->workspace)
-    return fail(LIST_ERR_ARG, "grad_sdf/packed_mlp_bwd/packed_mlp/workspace is NULL");
-  if (a->F != L.F) return fail(LIST_ERR_SHAPE, "F=%d but channels give %d", a->F, L.F);
-  if ((rc = check_hidden(a->H1, a->H2, a->H3))) return rc;
-  if (a->H1 > 2048 || a->H2 > 2048)
-    return fail(LIST_ERR_UNSUPPORTED, "backward supports hidden sizes up to 2048 (got %d/%d)", a->H1, a->H2);
-  if ((rc = check_precision(a->precision))) return rc;
-  if (ga->vox_adjoint < 0 || ga->vox_adjoint > 2) return fail(LIST_ERR_ARG, "vox_adjoint=%d", ga->vox_adjoint);
-  if (a->percep_proj) return fail(LIST_ERR_UNSUPPORTED, "a forward with percep_proj (inference) keeps no perceptual features for the backward");
-  if (a->img_proj) return fail(LIST_ERR_UNSUPPORTED, "a forward with img_proj (inference) keeps no perceptual features for the backward");
-  if (a->no_activations) return fail(LIST_ERR_ARG, "a forward with no_activations = 1 (inference) keeps no H1 / H2 for the backward");
+  FeatLayout L;
+  int64_t rows;
+  if (int rc = check_query_bwd(ga, &L, &rows)) return rc;
   const int64_t P = (int64_t)a->B * a->N;
-  if (P > kMaxChunkRows)
-    return fail(LIST_ERR_UNSUPPORTED, "backward handles up to %lld points per call (got %lld)",
-                (long long)kMaxChunkRows, (long long)P);
-  const int64_t rows = chunk_rows_for(a->workspace_bytes, P, L.Kp, a->H1, a->H2);
-  if (rows < P)
-    return fail(LIST_ERR_WORKSPACE, "forward workspace does not hold the whole query in one chunk");
   const bool fp16 = a->precision == LIST_PREC_FP16;
   const Workspace ws = workspace_layout(rows, L.Kp, a->H1, a->H2);
   const BwdWorkspace bw = bwd_workspace_layout(rows, L.Kp, a->H1, a->H2, a->H3, fp16);
-  if (ga->workspace_bytes < bw.total)
-    return fail(LIST_ERR_WORKSPACE, "backward workspace too small: %zu < %zu", ga->workspace_bytes, bw.total);
-  if (!aligned16(ga->workspace)) return fail(LIST_ERR_SHAPE, "workspace must be 16-byte aligned");
-  for (int l = 0; l < LIST_N_VOX_LEVELS; ++l) {
-    const ListVoxLevel& gv = ga->grad_vox[l];
-    if (!gv.data) continue;
-    const ListVoxLevel& v = a->vox[l];
-    if (gv.C != v.C || gv.D != v.D || gv.H != v.H || gv.W != v.W || gv.dtype != LIST_MAP_F32 ||
-        gv.image_stride != (int64_t)v.C * v.D * v.H * v.W)
-      return fail(LIST_ERR_SHAPE, "grad_vox[%d] must be fp32 [B][D][H][W][C] of the level's shape", l);
-  }
   const PackedMlp pk = packed_mlp_layout(L.Kp, a->H1, a->H2, a->H3);
   const PackedMlpBwd pb = packed_mlp_bwd_layout(L.Kp, a->H1, a->H2, a->H3);
   const char* wp = (const char*)a->packed_mlp;
@@ -876,26 +921,23 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   const bool lo = terms == 3;
   const int n_valid = (int)P;
   const int crow = (int)((P + kRowTile - 1) / kRowTile * kRowTile);
-  hipStream_t s = (hipStream_t)stream;
-  auto mark = [&](int stage) {
-    if (ga->stage_events && ga->stage_events[stage])
-      (void)hipEventRecord((hipEvent_t)ga->stage_events[stage], s);
+  const QueryBwdPlan plan = plan_bwd_for(ga, L, rows, bw.img_heavy_bytes);      // (query_bwd_plan.h: every lane and form below)
+  // lanes (VoxLane; see ListQueryGradArgs.aux_streams): the caller's stream and its auxiliary ones, as the plan maps them
+  const hipStream_t s = (hipStream_t)stream;
+  const hipStream_t given[4] = {s, (hipStream_t)ga->aux_streams[0], (hipStream_t)ga->aux_streams[1], (hipStream_t)ga->aux_streams[2]};
+  hipStream_t lane[4];
+  for (int l = 0; l < 4; ++l) lane[l] = given[plan.stream_of[l]];
+  auto mark = [&](int stage, hipStream_t on) {
+    if (ga->stage_events && ga->stage_events[stage]) (void)hipEventRecord((hipEvent_t)ga->stage_events[stage], on);
   };
   hipError_t e = hipSuccess;
   // a failure after the fork must not leave the auxiliary streams running past the call: the caller frees the
   // workspace and the outputs as soon as it sees the error.  join_and_fail() orders `s` behind whatever has been
   // enqueued on them so far, then reports.
-  hipStream_t j_direct = s, j_window = s, j_win2 = s;
-  hipEvent_t ev_dw0 = nullptr;                    // dW0 done (forked calls that want d_trans_mat)
+  hipEvent_t ev_dw0 = nullptr;                    // dW0 done (plan.dw0_event)
   auto join_and_fail = [&](hipError_t err, const char* what) -> int {
-    if (ev_dw0) { (void)hipEventDestroy(ev_dw0); ev_dw0 = nullptr; }
-    for (hipStream_t from : {j_direct, j_window, j_win2}) {
-      if (from == s) continue;
-      hipEvent_t ev;
-      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) continue;
-      if (hipEventRecord(ev, from) == hipSuccess) (void)hipStreamWaitEvent(s, ev, 0);
-      (void)hipEventDestroy(ev);
-    }
+    if (ev_dw0) (void)hipEventDestroy(ev_dw0);
+    (void)join_all(lane);
     return hip_fail(err, what);
   };
 #define LIST_TRY(call, what) do { e = (call); if (e != hipSuccess) return join_and_fail(e, what); } while (0)
@@ -905,42 +947,21 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   float* colsum = (float*)(bwp + bw.colsum);
   float* slab = (float*)(bwp + bw.slab);
   auto plane = [&](size_t off) { return (unsigned short*)(bwp + off); };
-
-  // optional fork/join onto the caller's auxiliary streams (see ListQueryGradArgs.aux_streams)
-  hipStream_t s_direct = s, s_window = s, s_win2 = s;
-  const bool forked = ga->aux_streams[0] && ga->aux_streams[1];
-  if (forked) { s_direct = (hipStream_t)ga->aux_streams[0]; s_window = (hipStream_t)ga->aux_streams[1]; }
-  if (forked && ga->aux_streams[2]) s_win2 = (hipStream_t)ga->aux_streams[2];
-  j_direct = s_direct; j_window = s_window; j_win2 = s_win2;
-  auto hand_over = [&](hipStream_t from, hipStream_t to) -> hipError_t {      // `to` continues after `from`'s work so far
-    if (from == to) return hipSuccess;
-    hipEvent_t ev;
-    hipError_t err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (err != hipSuccess) return err;
-    err = hipEventRecord(ev, from);
-    if (err == hipSuccess) err = hipStreamWaitEvent(to, ev, 0);
-    (void)hipEventDestroy(ev);                    // released once the wait has been satisfied
-    return err;
-  };
-  // The bias / fc_out.weight column sums feed nothing downstream: forked, they leave the chain of dependent GEMMs
-  // and run on the atomics' stream, which has nothing to do until dX exists (same kernels, same order among
-  // themselves -- they share the `colsum` scratch).
   auto side_colsum = [&](const unsigned short* z_hi, const unsigned short* z_lo, int N, const float* gsdf,
                          const int* ord, int use_inv_scale, float* out) -> hipError_t {
-    hipStream_t to = s;
-    if (forked) {
-      const hipError_t err = hand_over(s, s_direct);
-      if (err != hipSuccess) return err;
-      to = s_direct;
-    }
-    return launch_colsum(z_hi, z_lo, crow, n_valid, N, fmt, gsdf, ord, scale, use_inv_scale, colsum, out, to);
+    const hipError_t err = hand_over(s, lane[plan.colsum]);
+    if (err != hipSuccess) return err;
+    return launch_colsum(z_hi, z_lo, crow, n_valid, N, fmt, gsdf, ord, scale, use_inv_scale, colsum, out, lane[plan.colsum]);
   };
   ScatterParams sp;
   sp.g = make_gather(a, L, ws, 0, n_valid, crow);
   sp.g.order = order;
-  const bool pix = sort_has_pixel_order(*a);
-  if (pix) { sp.g.order_img = (const int*)(fw + ws.order_img); sp.g.row_of = (const int*)(fw + ws.row_of); }
-  sp.dx = bwp + bw.dx; sp.dx_f16 = fp16 ? 1 : 0; sp.scale = scale; sp.forked = forked ? 1 : 0;
+  const int* bins_pix = nullptr;                  // the forward's pixel bins, behind the Morton bins (a slot per image)
+  if (plan.pixel_order) {
+    sp.g.order_img = (const int*)(fw + ws.order_img); sp.g.row_of = (const int*)(fw + ws.row_of);
+    bins_pix = (const int*)(fw + ws.bins) + (size_t)a->B * kSortCells;
+  }
+  sp.dx = bwp + bw.dx; sp.dx_f16 = fp16 ? 1 : 0; sp.scale = scale; sp.forked = plan.forked ? 1 : 0;
   VoxGatherBuffers vb;
   vb.keys = (int*)(bwp + bw.vs_keys); vb.bins = (int*)(bwp + bw.vs_bins); vb.sums = (int*)(bwp + bw.vs_sums);
   vb.recs = bwp + bw.vs_recs; vb.mode = ga->vox_adjoint;
@@ -950,9 +971,8 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   vb.h16_bytes = fp16 ? (size_t)rows * a->H1 * 2 : 0;
   vb.h16w = fp16 ? (void*)(bwp + bw.dz2_lo) : nullptr;               // window levels: the dZ2 lo plane
   vb.h16w_bytes = fp16 ? (size_t)rows * a->H2 * 2 : 0;
-  const ScatterStreams sst = {s, s_direct, s_window, s_win2};
 
-  mark(LIST_BWD_BEGIN);
+  mark(LIST_BWD_BEGIN, s);
   // --- head: scale, dZ3, d fc_out (H3 = relu(fc_2) as the forward left it in its workspace) -------------------
   LIST_TRY(launch_grad_scale(ga->grad_sdf, P, fp16 ? 1 : 0, scale, ga->mlp.b3, colsum, s), "grad_scale launch");
   unsigned short* const h3_hi = (unsigned short*)(fw + ws.h3_hi);
@@ -964,7 +984,7 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   if (ga->mlp.b2)
     LIST_TRY(side_colsum(plane(bw.dz3_hi), lo ? plane(bw.dz3_lo) : nullptr, a->H3, nullptr, nullptr, 1, ga->mlp.b2),
              "d fc_2.bias launch");
-  mark(LIST_BWD_HEAD);
+  mark(LIST_BWD_HEAD, s);
 
   // one layer of the chain: weight gradient (TN), bias gradient, then the masked data gradient (NT)
   auto wgrad = [&](size_t dz_hi, size_t dz_lo, int M, const char* act_hi, const char* act_lo, int N, int ldb,
@@ -998,38 +1018,34 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
   };
 
   // fc_2
-  // (forked: the weight gradients feed nothing downstream either -- they queue up on the window stream, in the order
-  // dW2, dW1, dW0 because they share the split-K slab, while the data-gradient chain continues on `s`)
-  if (forked && ga->mlp.w2) LIST_TRY(hand_over(s, s_window), "stream fork");
+  if (plan.fork_dw2) LIST_TRY(hand_over(s, lane[plan.wgrad]), "stream fork");
   LIST_TRY(wgrad(bw.dz3_hi, bw.dz3_lo, a->H3, fw + ws.h2_hi, fw + ws.h2_lo, a->H2, a->H2, nullptr, ga->mlp.w2,
-                 a->H2, s_window), "dW2 launch");
-  mark(LIST_BWD_WGRAD2);
+                 a->H2, lane[plan.wgrad]), "dW2 launch");
+  mark(LIST_BWD_WGRAD2, s);
   LIST_TRY(dgrad(bw.dz3_hi, bw.dz3_lo, a->H3, wt + pb.w2t_hi, wt + pb.w2t_lo, a->H2, fw + ws.h2_hi, bw.dz2_hi,
                  bw.dz2_lo), "dH2 launch");
-  mark(LIST_BWD_DGRAD2);
+  mark(LIST_BWD_DGRAD2, s);
   // fc_1
   if (ga->mlp.b1)
     LIST_TRY(side_colsum(plane(bw.dz2_hi), lo ? plane(bw.dz2_lo) : nullptr, a->H2, nullptr, nullptr, 1, ga->mlp.b1),
              "d fc_1.bias launch");
-  if (forked && ga->mlp.w1) LIST_TRY(hand_over(s, s_window), "stream fork");
+  if (plan.fork_dw1) LIST_TRY(hand_over(s, lane[plan.wgrad]), "stream fork");
   LIST_TRY(wgrad(bw.dz2_hi, bw.dz2_lo, a->H2, fw + ws.h1_hi, fw + ws.h1_lo, a->H1, a->H1, nullptr, ga->mlp.w1,
-                 a->H1, s_window), "dW1 launch");
-  mark(LIST_BWD_WGRAD1);
+                 a->H1, lane[plan.wgrad]), "dW1 launch");
+  mark(LIST_BWD_WGRAD1, s);
   LIST_TRY(dgrad(bw.dz2_hi, bw.dz2_lo, a->H2, wt + pb.w1t_hi, wt + pb.w1t_lo, a->H1, fw + ws.h1_hi, bw.dz1_hi,
                  bw.dz1_lo), "dH1 launch");
-  mark(LIST_BWD_DGRAD1);
+  mark(LIST_BWD_DGRAD1, s);
   // fc_0
   if (ga->mlp.b0)
     LIST_TRY(side_colsum(plane(bw.dz1_hi), lo ? plane(bw.dz1_lo) : nullptr, a->H1, nullptr, nullptr, 1, ga->mlp.b0),
              "d fc_0.bias launch");
-  bool want_maps = ga->grad_img_map || ga->grad_trans_mat || ga->grad_percep_feat;
-  for (int l = 0; l < LIST_N_VOX_LEVELS; ++l) want_maps = want_maps || ga->grad_vox[l].data;
-  if (!want_maps) {
-    LIST_TRY(hand_over(s_window, s), "stream join");            // dW0 shares the slab with dW2 / dW1
-    LIST_TRY(wgrad(bw.dz1_hi, bw.dz1_lo, a->H1, fw + ws.x_hi, fw + ws.x_lo, L.Kp, L.Kp, &L, ga->mlp.w0, L.F, s),
+  if (plan.early) {
+    LIST_TRY(hand_over(lane[plan.wgrad], s), "stream join");            // dW0 shares the slab with dW2 / dW1
+    LIST_TRY(wgrad(bw.dz1_hi, bw.dz1_lo, a->H1, fw + ws.x_hi, fw + ws.x_lo, L.Kp, L.Kp, &L, ga->mlp.w0, L.F, lane[plan.dw0]),
              "dW0 launch");
-    for (int st = LIST_BWD_DGRAD0; st < LIST_N_BWD_STAGES; ++st) mark(st);
-    LIST_TRY(hand_over(s_direct, s), "stream join");
+    for (int st = LIST_BWD_DGRAD0; st < LIST_N_BWD_STAGES; ++st) mark(st, s);
+    LIST_TRY(hand_over(lane[plan.colsum], s), "stream join");
     return LIST_OK;
   }
   {
@@ -1042,68 +1058,42 @@ int list_sdf_query_bwd(const ListQueryGradArgs* ga, void* stream) {
     d.dx = bwp + bw.dx; d.dx_f16 = fp16 ? 1 : 0; d.n_store = L.Kp; d.ldo = L.Kp;
     LIST_TRY(launch_gemm(d, terms, EPI_DX, s), "dX launch");
   }
-  mark(LIST_BWD_DGRAD0);
+  mark(LIST_BWD_DGRAD0, s);
 
-  // dX is ready on `s`.  From here the work is a DAG of stages bound by different units: dW0 (MFMA; needs only
-  // dZ1 and X) and the 16^3 LDS-window level on one stream, the atomic-rate-bound levels on another, the 8^3 window level
-  // on the third (aux_streams[2]; without it, behind the gathers), the gathers (voxel-side gather, perceptual map,
-  // trans_mat) on `s`.  Without auxiliary streams: the same order, in line.
-  LIST_TRY(hand_over(s, s_direct), "stream fork");
-  LIST_TRY(hand_over(s, s_window), "stream fork");
-  LIST_TRY(hand_over(s, s_win2), "stream fork");
-  LIST_TRY(wgrad(bw.dz1_hi, bw.dz1_lo, a->H1, fw + ws.x_hi, fw + ws.x_lo, L.Kp, L.Kp, &L, ga->mlp.w0, L.F, s_window),
+  // --- fan-out: dX is ready on `s`, every lane continues behind it
+  for (int l = 1; l < 4; ++l) LIST_TRY(hand_over(s, lane[l]), "stream fork");
+  LIST_TRY(wgrad(bw.dz1_hi, bw.dz1_lo, a->H1, fw + ws.x_hi, fw + ws.x_lo, L.Kp, L.Kp, &L, ga->mlp.w0, L.F, lane[plan.dw0]),
            "dW0 launch");
-  mark(LIST_BWD_WGRAD0);
-  if (forked && ga->grad_trans_mat && !a->percep_feat) {        // (see the trans_mat gradient below)
+  mark(LIST_BWD_WGRAD0, s);
+  if (plan.dw0_event) {
     LIST_TRY(hipEventCreateWithFlags(&ev_dw0, hipEventDisableTiming), "event");
-    LIST_TRY(hipEventRecord(ev_dw0, s_window), "event");
+    LIST_TRY(hipEventRecord(ev_dw0, lane[plan.dw0]), "event");
   }
+  const ScatterStreams sst = {lane[0], lane[1], lane[2], lane[3]};
   LIST_TRY(launch_scatter_vox(sp, L, ga->grad_vox, vb, sst), "voxel scatter launch");
-  mark(LIST_BWD_VOX);
-  if (a->percep_feat) {
-    if (ga->grad_percep_feat)
-      LIST_TRY(launch_rows_to_grad(sp, L.img_off, L.img_C, a->B, (int*)(bwp + bw.vs_keys), ga->grad_percep_feat,
-                                   ga->gpf_sb, ga->gpf_sc, ga->gpf_sn, s), "grad_percep_feat launch");
-    mark(LIST_BWD_IMG); mark(LIST_BWD_TRANS);
-    LIST_TRY(hand_over(s_direct, s), "stream join");
-    LIST_TRY(hand_over(s_window, s), "stream join");
-    LIST_TRY(hand_over(s_win2, s), "stream join");
-    return LIST_OK;
-  }
-  const int nslots = a->B < kSortImages ? a->B : kSortImages;
-  const int* bins_pix = pix ? (const int*)(fw + ws.bins) + (size_t)nslots * kSortCells : nullptr;
-  if (pix && a->B > kSortImages) { sp.g.order_img = nullptr; sp.g.row_of = nullptr; bins_pix = nullptr; }
-  const int map_f16 = ga->grad_img_map_dtype == LIST_MAP_F16 ? 1 : 0;
-  // Forked, k_trans_grad must not run while dW0 does.  Whenever one of its waves shared a SIMD with the weight-gradient
-  // GEMM's (2 x 216 + 80 registers = the whole file in the split formats), ONE point's v-derivative came out different --
-  // d_trans_mat off by 1e-4 .. 7e-3 of its largest entry in 4 - 59 of 60 calls, depending on what else ran (tools/
-  // trans_noise_probe2.py, profiles/r04b_trans_mat_interference.txt: never with dW0 left out, never in line, never once
-  // the kernel held more registers or LDS than fit beside dW0; its inputs, its LDS records and every other gradient
-  // were bit-stable).  It was later localised to the one ds_bpermute pair of the kernel's loop, which is gone
-  // (bwd_scatter_kernels.hip); the order stays as a second fence and removes the overlap: map gradient, adjoint
-  // resize (it needs only the map gradient), then -- behind dW0's event -- the trans_mat gradient.  In line the stages
-  // keep their order (and their stage events their meaning).
-  // (LIST_BWD_TRANS_UNORDERED=1, diagnostic: the old order -- the stage right behind the map gradient, beside dW0 --
-  // for tools/trans_noise_probe2.py)
-  static const bool unordered = [] { const char* e = getenv("LIST_BWD_TRANS_UNORDERED"); return e && e[0] == '1'; }();
-  const bool split = forked && ga->grad_trans_mat && !unordered;
-  LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, bwp + bw.recs, ga->grad_img_map, map_f16,
-                           split ? nullptr : ga->grad_trans_mat, ga->stage_events, s, bwp + bw.img_heavy,
-                           bw.img_heavy_bytes), "image gradient launch");
-  if (ga->grad_img_levels)
-    LIST_TRY(launch_img_grad_to_levels(ga->grad_img_map, a->B, a->map_size, L.img_C, ga->grad_img_levels, s, map_f16,
-                                       scale), "img_grad_to_levels launch");
-  if (split) {
-    // ... on aux_streams[2] where there is one (idle once the 8^3 window level is done; s_win2 is `s` otherwise)
-    // instead of at the end of `s`: training step 6.43 -> 6.36 ms, 6.52 -> 6.32 with the points on the clamp
-    if (ev_dw0) LIST_TRY(hipStreamWaitEvent(s_win2, ev_dw0, 0), "stream order");
-    LIST_TRY(launch_img_grad(sp, L, *a, bins_pix, bwp + bw.recs, nullptr, map_f16, ga->grad_trans_mat,
-                             ga->stage_events, s_win2, nullptr, 0), "trans_mat gradient launch");
+  mark(LIST_BWD_VOX, s);
+  if (plan.rows_to_grad)
+    LIST_TRY(launch_rows_to_grad(sp, L.img_off, L.img_C, a->B, (int*)(bwp + bw.vs_keys), ga->grad_percep_feat,
+                                 ga->gpf_sb, ga->gpf_sc, ga->gpf_sn, s), "grad_percep_feat launch");
+  LIST_TRY(launch_img_map_grad(plan, sp, L, *a, a->B, bins_pix, bwp + bw.recs, ga->grad_img_map, bwp + bw.img_heavy, s),
+           "image gradient launch");
+  // the trans_mat gradient between its two stage events, on its lane
+  auto trans_stage = [&](hipStream_t on) -> hipError_t {
+    mark(LIST_BWD_IMG, on);
+    const hipError_t err = plan.trans == TRANSGRAD_NONE ? hipSuccess : launch_trans_grad(sp, L, *a, a->B, ga->grad_trans_mat, on);
+    mark(LIST_BWD_TRANS, on);
+    return err;
+  };
+  if (plan.trans != TRANSGRAD_BEHIND_DW0) LIST_TRY(trans_stage(s), "trans_mat gradient launch");
+  if (plan.resize)
+    LIST_TRY(launch_img_grad_to_levels(ga->grad_img_map, a->B, a->map_size, L.img_C, ga->grad_img_levels, s,
+                                       plan.resize_f16 ? 1 : 0, scale), "img_grad_to_levels launch");
+  if (plan.trans == TRANSGRAD_BEHIND_DW0) {
+    LIST_TRY(hipStreamWaitEvent(lane[plan.trans_lane], ev_dw0, 0), "stream order");
+    LIST_TRY(trans_stage(lane[plan.trans_lane]), "trans_mat gradient launch");
   }
   if (ev_dw0) { (void)hipEventDestroy(ev_dw0); ev_dw0 = nullptr; }
-  LIST_TRY(hand_over(s_direct, s), "stream join");
-  LIST_TRY(hand_over(s_window, s), "stream join");
-  LIST_TRY(hand_over(s_win2, s), "stream join");
+  LIST_TRY(join_all(lane), "stream join");
 #undef LIST_TRY
   return LIST_OK;
 }
@@ -1150,7 +1140,10 @@ int list_percep_pool_bwd(const ListPoolGradArgs* ga, void* stream) {
   sp.g.perm0 = 0; sp.g.perm1 = 1; sp.g.perm2 = 2; sp.g.scale = 1.f;
   sp.g.N = a->N; sp.g.p_begin = 0; sp.g.n_valid = (int)P; sp.g.rows = (int)rows; sp.g.Kp = a->img_C;
   sp.dx = dx; sp.dx_f16 = 0; sp.scale = scale;
-  e = launch_img_grad(sp, L, q, nullptr, recs, ga->grad_img_map, 0, ga->grad_trans_mat, nullptr, s);
+  const QueryBwdPlan plan = plan_query_bwd({&q, {}, ga->grad_img_map != nullptr, false, false, ga->grad_trans_mat != nullptr,
+                                            false, false, 0, rows, a->img_C, 0, false, /*pool=*/true});
+  e = launch_img_map_grad(plan, sp, L, q, a->B, nullptr, recs, ga->grad_img_map, nullptr, s);
+  if (e == hipSuccess && plan.trans != TRANSGRAD_NONE) e = launch_trans_grad(sp, L, q, a->B, ga->grad_trans_mat, s);
   if (e != hipSuccess) return hip_fail(e, "percep_pool_bwd launch");
   return LIST_OK;
 }
@@ -1162,7 +1155,7 @@ int list_img_map_grad_to_levels(const float* grad_img_map, int32_t B, int32_t ma
     return fail(LIST_ERR_SHAPE, "B=%d map_size=%d (need 2..320)", B, map_size);
   int Ct;
   if (int rc = check_img_levels(grads, false, "image level", &Ct)) return rc;
-  hipError_t e = launch_img_grad_to_levels(grad_img_map, B, map_size, Ct, grads, (hipStream_t)stream);
+  hipError_t e = launch_img_grad_to_levels(grad_img_map, B, map_size, Ct, grads, (hipStream_t)stream, 0, nullptr);
   if (e != hipSuccess) return hip_fail(e, "img_grad_to_levels launch");
   return LIST_OK;
 }

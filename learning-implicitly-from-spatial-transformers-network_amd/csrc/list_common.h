@@ -9,7 +9,8 @@
 
 #include "list_hip.h"
 #include "vox_adjoint_plan.h"       // kDisp (the stencil displacement) and what chooses a voxel level's adjoint form
-#include "query_fwd_plan.h"         // what chooses the forward's launches; kSortPixCells, kBoxPts
+#include "query_fwd_plan.h"         // what chooses the forward's launches; kSortImages, kSortPixCells, kBoxPts
+#include "query_bwd_plan.h"         // what chooses the backward's forms and streams behind the MLP chain; img_heavy_bytes
 
 namespace list {
 
@@ -264,18 +265,8 @@ inline PackedMlpBwd packed_mlp_bwd_layout(int Kp, int H1, int H2, int H3) {
 }
 
 // ---- backward workspace -----------------------------------------------------------------------------------
-constexpr int kSortImages = 64;          // image slots in the point sort's key (b % 64)
 constexpr int kColsumRows = 256;         // rows per partial of the bias-gradient column sums
 constexpr int kWgradMaxSplits = 128;
-
-// map-side gather of the perceptual-map gradient: chunks of its heavy groups (bwd_scatter_kernels.hip, kHeavyChunk =
-// 1024 candidates).  Every point is a candidate of at most 4 groups, so the chunks of groups above 1024 candidates
-// number at most 4 rows / 1024 whole ones plus one partial chunk per heavy group (<= 4 rows / 1024 of those).
-inline int img_heavy_max_chunks(int64_t rows) { return (int)(8 * rows / 1024 + 8); }
-inline size_t img_heavy_bytes(int64_t rows, int Ct) {
-  return 256 + (size_t)kSortImages * kSortPixCells * 4 + (size_t)img_heavy_max_chunks(rows) * 8 + 256 +
-         (size_t)img_heavy_max_chunks(rows) * 4 * Ct * 4;
-}
 
 struct BwdWorkspace {
   size_t scale;                              // float[4]: s, 1/s, sum(dsdf), -
@@ -521,7 +512,7 @@ hipError_t launch_colsum(const unsigned short* z_hi, const unsigned short* z_lo,
                          int N, int fmt, const float* grad_sdf, const int* order, const float* scale,
                          int use_inv_scale, float* partial, float* out, hipStream_t s);
 
-// backward: maps (bwd_scatter_kernels.hip)
+// backward: the voxel levels (bwd_scatter_kernels.hip)
 struct ScatterParams {
   GatherParams g;             // points (x_hi/x_lo unused)
   const void* dx; int dx_f16; // [rows][Kp]
@@ -540,19 +531,19 @@ hipError_t launch_scatter_vox_box(const ScatterParams& sp, const ListVoxLevel& g
 struct ScatterStreams { hipStream_t gather, direct, window, window2; };     // the adjoint forms' streams (VoxLane)
 hipError_t launch_scatter_vox(const ScatterParams& sp, const FeatLayout& L, const ListVoxLevel grad_vox[LIST_N_VOX_LEVELS],
                               const VoxGatherBuffers& vb, const ScatterStreams& st);
-// map_f16: grad_img_map receives halfs at the gradient scale (the intermediate of the adjoint resize, fp16 operands)
-// heavy / heavy_bytes: scratch of the map-side gather's heavy groups (img_heavy_bytes(); null: every group is walked by
-// its own workgroup)
-hipError_t launch_img_grad(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
-                           const int* bins_pix, void* recs, float* grad_img_map, int map_f16,
-                           float* grad_trans_mat, void* const* stage_events, hipStream_t s, void* heavy = nullptr,
-                           size_t heavy_bytes = 0);
+
+// backward: the 2-D adjoints (bwd_img_kernels.hip), which execute plan_query_bwd (query_bwd_plan.h); B: images the points reach
+// the map gradient: recs = 32 B per row of scratch; bins_pix, heavy: the gather form's pixel bins and heavy-group scratch
+hipError_t launch_img_map_grad(const QueryBwdPlan& plan, const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a,
+                               int B, const int* bins_pix, void* recs, float* grad_img_map, void* heavy, hipStream_t s);
+hipError_t launch_trans_grad(const ScatterParams& sp, const FeatLayout& L, const ListQueryArgs& a, int B,
+                             float* grad_trans_mat, hipStream_t s);
 hipError_t launch_rows_to_grad(const ScatterParams& sp, int img_off, int C, int B, int* row_of_scratch, float* out,
                                int64_t sb, int64_t sc, int64_t sn, hipStream_t s);
 hipError_t launch_grad_to_rows(const float* src, int64_t sb, int64_t sc, int64_t sn, int B, int N, int C, float* dx,
                                float* scale, hipStream_t s);
 hipError_t launch_img_grad_to_levels(const float* grad_img_map, int B, int map_size, int Ct,
-                                     const ListMap2D grads[LIST_N_IMG_LEVELS], hipStream_t s, int map_f16 = 0,
-                                     const float* scale = nullptr);
+                                     const ListMap2D grads[LIST_N_IMG_LEVELS], hipStream_t s, int map_f16,
+                                     const float* scale);
 
 }  // namespace list

@@ -141,4 +141,25 @@ __device__ __forceinline__ RowProjRec row_proj_rec(const GatherParams& g, const 
   return r;
 }
 
+// ---- dX and map taps as floats (the backward's adjoints) --------------------------------------
+template <int DXH>
+__device__ __forceinline__ float dx_at(const void* __restrict__ dx, int64_t i) {
+  return DXH ? h2f(((const unsigned short*)dx)[i]) : ((const float*)dx)[i];
+}
+
+// 8 consecutive channels of a map tap / of dX as floats (one or two 16-B loads)
+template <int F16>
+__device__ __forceinline__ void load8(const void* __restrict__ base, int64_t i, float (&f)[8]) {
+  if (F16) {
+    const uint4 r = *(const uint4*)((const unsigned short*)base + i);
+    f[0] = h2f((unsigned short)(r.x & 0xffff)); f[1] = h2f((unsigned short)(r.x >> 16));
+    f[2] = h2f((unsigned short)(r.y & 0xffff)); f[3] = h2f((unsigned short)(r.y >> 16));
+    f[4] = h2f((unsigned short)(r.z & 0xffff)); f[5] = h2f((unsigned short)(r.z >> 16));
+    f[6] = h2f((unsigned short)(r.w & 0xffff)); f[7] = h2f((unsigned short)(r.w >> 16));
+  } else {
+    const float4 a = *(const float4*)((const float*)base + i), b = *(const float4*)((const float*)base + i + 4);
+    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+  }
+}
+
 }  // namespace list

@@ -12,6 +12,7 @@
 
 namespace list {
 
+constexpr int kSortImages = 64;       // image slots in the point sort's key (b % 64)
 constexpr int kSortPixCells = 8192;   // pixel-order bins per image of the point sort (>= ms * ceil(ms / 4))
 constexpr int kBoxPts = 64;           // points per workgroup of the matrix-core gather (gather_box_kernels.hip)
 

@@ -734,7 +734,7 @@ def sdf_query_backward(ctx, grad_sdf, packed_bwd, want_mlp=True, want_img=True, 
         out["mlp"] = m
     keep = []
     if want_img:
-        # (restates sort_has_pixel_order, csrc/query_fwd_plan.h, and kSortImages = 64: where it is wrong the library refuses)
+        # (restates map_grad_gathers, csrc/query_bwd_plan.h, with kSortImages = 64: where it is wrong the library refuses)
         half_map = (not want_img_map and img_levels_like is not None and a.precision == PREC_FP16 and not a.no_sort
                     and B <= 64 and a.map_size * ((a.map_size + 3) // 4) <= 8192 and a.img_C % 4 == 0)
         if half_map:

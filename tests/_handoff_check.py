@@ -1,5 +1,5 @@
 """The per-element check of the layout hand-off kernels (prep_kernels.hip: the 2-D resize, the voxel transposes, the
-projected perceptual map; bwd_scatter_kernels.hip: the adjoint resize), shared by test_handoff_cpu.py (which applies it to
+projected perceptual map; bwd_img_kernels.hip: the adjoint resize), shared by test_handoff_cpu.py (which applies it to
 numpy fp32 restatements and to deliberately wrong ones) and test_handoff_gpu.py (which applies it to every dispatch branch
 of the device).  Plain numpy; no GPU here.
 

@@ -1,6 +1,6 @@
 """GPU: the layout hand-off kernels on every dispatch branch, element by element against the float64 references and the
 derived bounds of tests/_handoff_check.py -- the 2-D resize (prep_kernels.hip: k_prep_img, k_prep_img_tile<0/1>,
-k_prep_img_nhwc<0/1>, k_prep_img_rows<0/1> in its three load forms), the adjoint resize (bwd_scatter_kernels.hip:
+k_prep_img_nhwc<0/1>, k_prep_img_rows<0/1> in its three load forms), the adjoint resize (bwd_img_kernels.hip:
 k_img_grad_level<0>), the voxel transposes (k_transpose_vox, the fused tile launch, the elementwise conversion) and the
 projected perceptual map (k_img_level_rows<0/1>, the grouped projection, k_proj_resize_sum for one to five levels).
 Every element of every output is compared; every test prints its worst error / bound (a record, not a tolerance)."""

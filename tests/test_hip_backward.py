@@ -171,6 +171,47 @@ def test_backward_is_independent_of_point_order_and_partial_outputs(hip, golden_
         assert rel_max(only_maps[k], a[k]) < 1e-5, k
 
 
+@pytest.mark.parametrize("precision", ["fp16", "bf16x3"])
+def test_forked_and_in_line_calls_give_the_same_bits(hip, precision):
+    """One saved forward context (B = 2, N = 300: three 256-row tiles, the last one padded), the backward in every order of
+    csrc/query_bwd_plan.h a Python call reaches: in line; forked; forked without the trans_mat gradient (no dW0 event); and
+    in line / forked with the adjoint resize inside the call.  The outputs that are summed in a fixed order -- the eight MLP
+    gradients, the gathered map gradient, the five encoder levels -- are bit-identical between the in-line and the forked
+    calls (tools/bwd_stream_screen.py at the benchmark's size): a hand-over missing between two streams would show up here.
+    Not the voxel levels: they are summed with atomics, their bits vary from run to run."""
+    c = cases._case(4100, batch=2, n=300, img_res=32, vox_res=16)
+    md = hip.map_dtype_for(precision)
+    img_in = [dev(m) for m in c["img_maps"]]
+    img = hip.prep_img_maps(img_in, 137, dtype=md)
+    vox = hip.prep_vox_maps([dev(m) for m in c["vox_maps"]], dtype=md)
+    params = {k: dev(v) for k, v in c["weights"].items()}
+    packed = hip.prep_mlp_weights(params, vox.channels, img.channels, precision)
+    packed_b = hip.prep_mlp_weights_bwd(params, vox.channels, img.channels, precision)
+    sdf, ctx = hip.sdf_query(dev(c["query"]), dev(c["trans_mat"]), img, vox, packed, precision=precision,
+                             save_for_backward=True)
+    gsdf = dev(synth.normalish(4101, tuple(sdf.shape))) / sdf.shape[0]
+
+    def run(**want):
+        o = hip.sdf_query_backward(ctx, gsdf, packed_b, **want)
+        torch.cuda.synchronize()
+        det = dict(o["mlp"], img_map=o["img_map"])
+        det.update({f"img_level{i}": t for i, t in enumerate(o.get("img_levels", []))})
+        return det
+
+    inline = run(overlap=False)
+    inline_levels = run(overlap=False, img_levels_like=img_in)
+    assert len(inline) == 9 and len(inline_levels) == 14
+    assert all(bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0 for v in inline_levels.values())
+    for name, got in [("forked", run(overlap=True)), ("forked, no trans_mat", run(overlap=True, want_trans=False)),
+                      ("in line, levels in the call", inline_levels),
+                      ("forked, levels in the call", run(overlap=True, img_levels_like=img_in))]:
+        ref = inline_levels if len(got) == 14 else inline
+        for k in got:
+            assert torch.equal(got[k], ref[k]), (name, k)
+        for k in inline:
+            assert torch.equal(got[k], inline[k]), (name, k)
+
+
 def test_backward_on_the_real_map_sizes_against_the_oracle(hip):
     """137^2 x 1024 map from 224^2 encoder levels (down- AND up-sampled levels), 128^3 voxel levels:
     oracle autograd on the CPU, a few points."""
@@ -572,7 +613,7 @@ def test_module_forms_differentiate_through_hip(hip, golden_dir):
 def test_image_gradient_with_projections_piled_onto_the_clamp(hip):
     """Thousands of points on one pixel (network/modules.py:43 clamps what leaves the map; an untrained spatial
     transformer sends ~90 % of the points there): the map-side gather cuts such a pixel group into chunks summed by
-    separate workgroups (bwd_scatter_kernels.hip, kHeavyChunk = 1024 candidates).  Checked against (a) the atomic form of
+    separate workgroups (bwd_img_kernels.hip, kHeavyChunk = 1024 candidates).  Checked against (a) the atomic form of
     the same gradient, which the unsorted forward takes (no pixel order, no groups), and (b) the oracle's autograd."""
     seed, B, N = 7711, 2, 2600
     c = {"query": synth.make_query(seed, B, N), "img_maps": synth.make_img_maps(seed, B, 32),
